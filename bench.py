@@ -8,15 +8,31 @@ the gap, backward, (DP: SUM all-reduce of gradients + SyncBN), Adam step --
 i.e. models/CNNBLSTM/train.py:83-108 with the dataset of
 models/CNNBLSTM/dataset.py:93-119 moved onto the GPU.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
 Prints ONE JSON line (rank 0).  value = frames processed by all ranks / max
-over ranks of the timed wall time.  Also reports:
-  roofline     the dominant kernel (the LSTM layer-0 input-projection GEMM,
-               M=N*T, N=8H, K=C*F) timed live with HIP events on its stream;
+over ranks of the timed wall time; ms_per_step = that wall time / K.
+
+A plain run sets up, warms up, times the K steps, writes the last timed
+step's outputs if --dump-outputs is given, and prints the result line.
+--full adds the measurements that take runs of their own (their keys are
+null in a plain run's line):
+  graph        the same step captured in a HIP graph and replayed (N=1);
+  recon_l1     the reference test loss on a fixed 64-clip eval set;
+  roofline*    the dominant kernel (the LSTM layer-0 input-projection GEMM,
+               M=N*T, N=8H, K=C*F), the layer-0 backward pair and the STFT
+               kernel timed live with HIP events on their stream;
+  in_step_kernels  the committed per-step kernel tables (profiles/steps/);
+  dp           the gradient all-reduce alone and the compute-only step (N>1);
   cpu_baseline the oracle's torch-CPU restatement of the same step (the
                reference's CPU path), on a bounded sample, rank 0 at N=1 only.
+
+--dump-outputs DIR (rank 0): DIR/<name>.npy, float32, of what the last timed
+step handed back -- the model output, the losses, and the gradients and
+updated parameters (tensors above DUMP_SAMPLE elements as a fixed seeded
+sample).  Inputs and initial weights are seeded, so two builds run with the
+same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -60,6 +76,39 @@ def _traffic(name):
 def synthetic_clips(n, S, seed0):
     from ainp.synth import synthetic_clip
     return np.stack([synthetic_clip(seed0 + i, S) for i in range(n)])
+
+
+DUMP_FULL = 3 << 20            # elements kept of a step output (C2's y: 2.75 M)
+DUMP_SAMPLE = 1 << 16          # elements kept of a parameter / gradient
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs, model_state=()):
+    """--dump-outputs: path/<name>.npy (float32) of `outputs` {name: tensor}
+    (kept whole up to DUMP_FULL elements) and of `model_state`, (name, tensor)
+    pairs of gradients / parameters (whole up to DUMP_SAMPLE elements).  A
+    larger tensor is written as a sample of that many elements at flat
+    indices drawn from a generator seeded by its name, the same in every run."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    todo = [(n, t, DUMP_FULL) for n, t in outputs.items()]
+    todo += [(n, t, DUMP_SAMPLE) for n, t in model_state]
+    for name, t, cap in todo:
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        if t.numel() > cap:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would exceed {DUMP_LIMIT_BYTES} bytes "
+                             f"at {name}")
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def host_cpu():
@@ -568,7 +617,8 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32, help="examples per GPU (C2: 32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--roofline-reps", type=int, default=10)
     ap.add_argument("--workload", choices=("cnnblstm", "gan"), default="cnnblstm",
@@ -576,10 +626,15 @@ def main():
     ap.add_argument("--clip-s", type=float, default=None,
                     help="gan: clip length (5 s = C4, T=626; 8 s = C5, T=1001, 0.1 s gap)")
     ap.add_argument("--no-graph", action="store_true",
-                    help="skip the HIP-graph replay measurement of the same step (N=1)")
+                    help="with --full: skip the HIP-graph replay measurement of the same step (N=1)")
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32",
                     help="fp32 = C2 (headline); bf16 = the C3 per-GPU shape (bf16 GEMM/conv "
                          "operands, fp32 accumulate / cell state / BN statistics / weights)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: HIP-graph replay, eval recon L1, live "
+                         "rooflines, in-step kernel tables, DP accounting, CPU baseline")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: one rank per GPU, started here before this
@@ -627,6 +682,7 @@ def main():
     rng = np.random.default_rng(12345 + rank)
     starts = torch.from_numpy(rng.integers(0, S - g, size=(nsteps, B)).astype(np.int64)).to(dev)
     losses = torch.zeros(nsteps, device=dev)
+    last = {}                               # --dump-outputs: the last timed step's tensors
 
     def step(i):
         with phase("data"):
@@ -643,6 +699,8 @@ def main():
         with phase("optimizer"):
             opt.step()
         losses[i] = loss.detach()
+        if args.dump_outputs and i == nsteps - 1:
+            last.update(features=x, target=tgt, mask=mask, y=y.detach(), loss=loss.detach())
 
     for i in range(args.warmup):
         step(i)
@@ -670,11 +728,19 @@ def main():
     ms_step = 1000.0 * elapsed / args.steps
     train_loss = float(losses[-1].item())
 
+    if args.dump_outputs and rank == 0:
+        # before anything below trains the model further (the graph replay)
+        last["losses"] = losses[args.warmup:]
+        named = list(model.named_parameters())
+        dump_outputs(args.dump_outputs, last,
+                     [("grad." + n, p.grad) for n, p in named if p.grad is not None]
+                     + [("param." + n, p) for n, p in named])
+
     # ---- DP accounting (N > 1): the gradient all-reduce alone, the step
     # without it (compute only, SyncBN kept), and how much of the all-reduce
     # the backward hid: overlap = 1 - (step - compute) / allreduce
     dp = None
-    if world > 1:
+    if world > 1 and args.full:
         grads = [p.grad for p in model.parameters() if p.grad is not None]
         big = [g for g in grads if g.numel() * 4 >= reducer.bucket_bytes]
         small = torch.cat([g.reshape(-1) for g in grads if g.numel() * 4 < reducer.bucket_bytes])
@@ -708,9 +774,10 @@ def main():
                         "in 8 gate chunks all-reduced as each completes",
               "backend": dist.get_backend()}
     graph = None
-    if world == 1 and not args.no_graph:
+    if args.full and world == 1 and not args.no_graph:
         graph = graph_replay(model, opt, audio, starts, g, n_fft, hop, win, T, args, dev, med_ms)
-    recon_l1 = eval_recon_l1(model, n_fft, hop, win, T, S, g, dev) if rank == 0 else None
+    recon_l1 = (eval_recon_l1(model, n_fft, hop, win, T, S, g, dev)
+                if args.full and rank == 0 else None)
 
     # ---- roofline: dominant kernel (LSTM layer-0 input projection GEMM) timed
     # live, and the layer-0 backward pair (data + weight gradient) as the step
@@ -718,14 +785,14 @@ def main():
     # issues, so frac <= 1 by construction: bf16 -> the dense bf16 MFMA peak;
     # fp32 (x6: 6 bf16 MFMA products per fp32 product) -> bf16 peak / 6.
     roof = roof_bwd = None
-    if rank == 0:
+    if args.full and rank == 0:
         H = CFG["model"]["lstm_hidden_dim"]
         I = (H // 2) * (n_fft // 2 + 1)
         roof, roof_bwd = l0_rooflines(model, B, T, H, I, bf16, args.roofline_reps, dev)
 
     # ---- STFT / feature / mask path (HBM-bound): 4880 B per frame
     roof_stft = None
-    if rank == 0:
+    if args.full and rank == 0:
         st_s = time_kernel(lambda: ops.stft_features(audio, starts[0], g, n_fft, hop, win,
                                                      n_frames=T), args.roofline_reps, dev)
         st_bytes = 4880 * B * T
@@ -738,7 +805,7 @@ def main():
                      "avg_launch_ms": round(st_s * 1e3, 4), "bytes_per_launch": st_bytes}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_batch, T)
 
     if rank == 0:
@@ -774,7 +841,8 @@ def main():
                 step_flops / world / (ms_step / 1e3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4)}),
             "roofline": roof,
             "roofline_l0_bwd": roof_bwd,
-            "in_step_kernels": in_step_table(("cnnblstm", args.dtype), bf16),
+            "in_step_kernels": (in_step_table(("cnnblstm", args.dtype), bf16)
+                                if args.full else None),
             "roofline_stft": roof_stft,
             "dp": dp,
             "graph": graph,
@@ -896,7 +964,7 @@ def run_gan(args):
                                              mode=ops.FEAT_GAN, outputs=(True, True, c5, True))
         out = tr.step(o.unsqueeze(1), im.unsqueeze(1), m.unsqueeze(1))
         hole[i] = out["g_l1_hole"]
-        last.update(orig=o, imp=im, phase=ph, mask=m, gen=out["generated"])
+        last.update(orig=o, imp=im, phase=ph, mask=m, gen=out["generated"], out=out)
 
     for i in range(args.warmup):
         step(i)
@@ -921,6 +989,15 @@ def run_gan(args):
     value = B * T * args.steps * world / elapsed
     ms_step = 1000.0 * elapsed / args.steps
 
+    if args.dump_outputs and rank == 0:
+        # what GanTrainer.step returned for the last timed batch (generated
+        # spectrogram + every loss), its features, and D's updated parameters
+        outs = {k: v for k, v in last["out"].items() if torch.is_tensor(v)}
+        outs.update(original=last["orig"], impaired=last["imp"], mask=last["mask"],
+                    g_l1_hole_steps=hole[args.warmup:])
+        dump_outputs(args.dump_outputs, outs,
+                     [("param.D." + n, p) for n, p in disc.named_parameters()])
+
     # C5: on-GPU audio reconstruction of the last batch, the sample path of
     # models/GAN/train.py:465-505: combined log-magnitude (generated in the
     # hole, original elsewhere; passed to utils.spectrogram_to_audio as the
@@ -929,8 +1006,8 @@ def run_gan(args):
     # without phase; timed separately: the reference runs it every
     # sample_interval steps, not per step
     recon = None
-    if c5 and rank == 0:
-        mag = (last["gen"][:, 0] * (1 - last["mask"]) + last["orig"] * last["mask"]).contiguous()
+    if args.full and c5 and rank == 0:
+        mag =(last["gen"][:, 0] * (1 - last["mask"]) + last["orig"] * last["mask"]).contiguous()
         ist_s = time_kernel(lambda: ops.istft(mag=mag, phase=last["phase"], n_fft=n_fft,
                                               hop_length=hop), 5, dev)
         gl_s = time_kernel(lambda: ops.griffinlim(mag, n_iter=64, hop_length=hop, n_fft=n_fft,
@@ -944,7 +1021,7 @@ def run_gan(args):
                  "batch": B, "samples_per_clip": hop * (T - 1)}
 
     roof = roof_wide = None
-    if rank == 0:
+    if args.full and rank == 0:
         # the in-step launches of the two dominant conv kernels, on operands
         # captured from a G forward over the last timed batch (real masks and
         # window ratios): the final PartialConv2d (65 -> 64, 3x3) at the padded
@@ -981,7 +1058,7 @@ def run_gan(args):
             roof_wide["main_loop"] = ("256x128 tiles, 8 waves of 64x64, 3-stage LDS-DMA ring "
                                       "(global_load_lds_dwordx4), v_mfma_f32_32x32x16_bf16")
     families = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # per-family algorithmic work of one step, as the step routes it
         ops.WORK_TRACE = []
         step(nsteps - 1)
@@ -991,7 +1068,7 @@ def run_gan(args):
             families[nm] = families.get(nm, 0.0) + fl
         ops.WORK_TRACE = None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = gan_cpu_baseline(T, S, g)
     if rank == 0:
         step_flops = GAN_FLOP_PER_SAMPLE[T] * B * world if T in GAN_FLOP_PER_SAMPLE else None
@@ -1018,7 +1095,8 @@ def run_gan(args):
             "mfma_util_step": (round(step_flops / world / (ms_step / 1e3) / 1e12
                                      / executed_peak(bf16), 4) if step_flops else None),
             "roofline": roof, "roofline_wide": roof_wide, "reconstruction": recon,
-            "in_step_kernels": in_step_table(("gan", args.dtype, T), bf16, families=families),
+            "in_step_kernels": (in_step_table(("gan", args.dtype, T), bf16, families=families)
+                                if args.full else None),
             "cpu_baseline": cpu,
         }
         print(json.dumps(out), flush=True)

@@ -21,9 +21,9 @@ step() {  # step <seconds> <logfile> cmd...
 if [ "$TESTS" = tests ]; then
   step 600 pytest_gpu.log python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread || exit 1
 fi
-step 300 bench.json python bench.py || exit 1
+step 300 bench.json python bench.py --full || exit 1
 step 200 opbench.log python tools/cnnblstm_op_bench.py || exit 1
 step 300 prof.log rocprofv3 --kernel-trace --stats -f csv rocpd -d "$OUT/prof" -o run -- \
-  python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline || exit 1
-step 300 bench_gan.json python bench.py --workload gan || exit 1
+  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline || exit 1
+step 300 bench_gan.json python bench.py --full --workload gan || exit 1
 echo "all steps ok"

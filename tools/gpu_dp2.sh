@@ -12,7 +12,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_dist.py -x -v --timeout 300
 tail -1 "$OUT/pytest_dist.log"; [ $rc -eq 0 ] || exit 1
 for dt in fp32 bf16; do
   AINP_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline \
+    --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline \
     --no-graph --dtype $dt > "$OUT/dp2_gloo_$dt.json" 2> "$OUT/dp2_gloo_$dt.err" || exit 1
   tail -1 "$OUT/dp2_gloo_$dt.json" | cut -c1-200
 done

@@ -15,6 +15,6 @@ step() {
   return $rc
 }
 step 900 pytest_gpu.log python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread || exit 1
-step 300 bench.json python bench.py || exit 1
-step 300 bench_bf16.json python bench.py --dtype bf16 --no-cpu-baseline || exit 1
+step 300 bench.json python bench.py --full || exit 1
+step 300 bench_bf16.json python bench.py --full --dtype bf16 --no-cpu-baseline || exit 1
 echo "all steps ok"

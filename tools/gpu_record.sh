@@ -24,11 +24,11 @@ if [ "$PART" = tests ]; then
   step 1000 pytest_gpu.log python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread || exit 1
   step 300 smoke.log python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" || exit 1
 else
-  step 300 bench_c2.json python bench.py || exit 1
-  step 300 bench_c3.json python bench.py --dtype bf16 || exit 1
-  step 400 bench_gan_c4.json python bench.py --workload gan --dtype bf16 || exit 1
-  step 400 bench_gan_c5.json python bench.py --workload gan --dtype bf16 --clip-s 8 || exit 1
+  step 300 bench_c2.json python bench.py --full || exit 1
+  step 300 bench_c3.json python bench.py --full --dtype bf16 || exit 1
+  step 400 bench_gan_c4.json python bench.py --full --workload gan --dtype bf16 || exit 1
+  step 400 bench_gan_c5.json python bench.py --full --workload gan --dtype bf16 --clip-s 8 || exit 1
   step 300 prof_c2.log rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof_c2" -o run -- \
-    python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline || exit 1
+    python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline || exit 1
 fi
 echo "all steps ok"
