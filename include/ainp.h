@@ -524,6 +524,11 @@ int ainp_conv3x3_dgrad_bnr(const float* dy, const float* w, float* dx, int64_t N
                            int Cout, int64_t H, int64_t W, int flags, const void* y,
                            const float* scale, const float* shift, const float* save_mean_rstd,
                            void* workspace, double* sums, int bn_flags, void* stream);
+/* 1 if ainp_conv3x3_dgrad_bnr with this shape, `flags` and `bn_flags` takes
+ * dx == NULL (host-only: the routing's answer, so a caller need not know
+ * which kernel serves the partials-only form). */
+int ainp_conv3x3_dgrad_bnr_nodx_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W, int flags,
+                                   int bn_flags);
 
 /* bf16 configuration (BASELINE C3): the encoder's last BN+ReLU writes the
  * layer-0 LSTM input directly as bf16 (nearest-even) in both layouts the

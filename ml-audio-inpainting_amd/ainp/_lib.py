@@ -88,6 +88,8 @@ _SIGS = {
     "ainp_conv3x3_io16_ok": (c_int, [c_int64, c_int, c_int, c_int64, c_int64]),
     "ainp_conv3x3_cl_ok": (c_int, [c_int64, c_int, c_int, c_int64, c_int64]),
     "ainp_conv3x3_dgrad_cfnt_ok": (c_int, [c_int64, c_int, c_int, c_int64, c_int64]),
+    "ainp_conv3x3_dgrad_bnr_nodx_ok": (c_int, [c_int64, c_int, c_int, c_int64, c_int64, c_int,
+                                               c_int]),
     "ainp_conv3x3_dgrad_bnapply": (c_int, [P, P, P, P, P, P, P, P, c_int64, P, c_int, P, P,
                                            c_int64, c_int, c_int, c_int64, c_int64, P]),
     "ainp_conv3x3_wgrad_bnapply": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int64, P, P, P, P, P,

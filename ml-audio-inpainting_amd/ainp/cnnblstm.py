@@ -288,10 +288,11 @@ class _ConvStackFn(torch.autograd.Function):
                 # dx channel-last into a BatchNorm+ReLU: its backward reduce
                 # is summed by the data gradient's epilogue
                 psc, psh, psv = ctx.affine[bi - 1]
-                if (FUSE_BNA6 and tuple(w.shape[:2]) == (1, 16) and not ycl
-                        and gy.dtype == torch.float32 and ys[bi - 1].dtype == torch.float32):
+                if (FUSE_BNA6 and not ycl and ys[bi - 1].dtype == torch.float32
+                        and ops.dgrad_bnr_nodx_ok(gy, w, ys[bi - 1], bf16=ctx.bf16, xcl=ycl)):
                     # round 6: Conv2d(16, 1) -- the sums now, dx recomputed by the
-                    # apply (ops.conv3x3_dgrad_bnapply): never written or read back
+                    # apply (ops.conv3x3_dgrad_bnapply, which takes dy [N, 1, H, W]
+                    # and an fp32 y): never written or read back
                     _, pre_sums = ops.conv3x3_dgrad_bnr(gy, w, ys[bi - 1], psc, psh, psv,
                                                         bf16=ctx.bf16, xcl=ycl, want_dx=False)
                     g, pend = None, (gy, w)
@@ -314,8 +315,7 @@ class _ConvStackFn(torch.autograd.Function):
 # Round 6: the decoder's last conv (16 -> 1): its data gradient only sums the
 # BatchNorm reduce of decoder.5, and that layer's apply recomputes it
 # (AINP_FUSE_BNA6=0: dx written and read back)
-FUSE_BNA6 = (os.environ.get("AINP_FUSE_BNA6", "1") != "0"
-             and os.environ.get("AINP_SMALL_ROWS", "1") != "0")   # the row-strip kernel
+FUSE_BNA6 = os.environ.get("AINP_FUSE_BNA6", "1") != "0"
 
 
 # Round 6: the encoder's first conv (1 -> 16) weight gradient with its

@@ -861,13 +861,26 @@ def dgrad_cfnt_ok(N, Cin, Cout, H, W) -> bool:
     return bool(_lib.lib.ainp_conv3x3_dgrad_cfnt_ok(N, Cin, Cout, H, W))
 
 
+def dgrad_bnr_nodx_ok(dy, w, y, bf16=False, xcl=False) -> bool:
+    """ainp_conv3x3_dgrad_bnr_nodx_ok: conv3x3_dgrad_bnr(dy, w, y, ..., bf16=bf16,
+    xcl=xcl, want_dx=False) is served (the library's routing says for which
+    convs, dtypes and settings)."""
+    if xcl:
+        N, H, W, Cout = dy.shape
+    else:
+        N, Cout, H, W = dy.shape
+    return bool(_lib.lib.ainp_conv3x3_dgrad_bnr_nodx_ok(
+        N, w.shape[1], Cout, H, W, _dy_flags(dy, bf16) | (CONV_XCL if xcl else 0) | CONV_YCL,
+        _y_flag(y)))
+
+
 def conv3x3_dgrad_bnr(dy, w, y, scale, shift, save, bf16=False, xcl=False, want_dx=True):
     """The data gradient (dx channel-last [N, H, W, Cin]) and the reduce step
     of the BatchNorm+ReLU backward it feeds (ainp_conv3x3_dgrad_bnr): y is that
     layer's pre-BatchNorm output [N, H, W, Cin] (fp32 or bf16 storage).
     Returns (dx, sums) -- sums as bn_relu_bwd_reduce(dx, y, ..., cl=True).
-    want_dx=False (Conv2d(16, 1), round 6): dx is not written (returned None);
-    conv3x3_dgrad_bnapply recomputes it into the apply."""
+    want_dx=False (Conv2d(16, 1), round 6; where dgrad_bnr_nodx_ok): dx is not
+    written (returned None); conv3x3_dgrad_bnapply recomputes it into the apply."""
     _req(dy, "dy", None); _req(w, "w"); _req(y, "y", None)
     if xcl:
         N, H, W, Cout = dy.shape

@@ -18,12 +18,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_route.h"
 
 namespace ainp {
 
 // ---------------------------------------------------------------- forward
-constexpr int CV_FT = 8;          // rows per tile
-constexpr int CV_TT = 48;         // columns per tile (3 MFMA tiles)
+// (CV_FT x CV_TT output tiles: conv_route.h)
 constexpr int CV_CK = 8;          // input channels per K chunk
 constexpr int CV_LDT = 52;        // LDS row length (>= TT+2)
 constexpr int CV_PLANE = 528;     // >= (FT+2)*LDT, == 16 mod 32 (conflict-free A)
@@ -267,7 +267,6 @@ constexpr int WG_FT = 2, WG_TT = 64;
 constexpr int WG_LDT = 68;         // >= TT+2
 constexpr int WG_XPLANE = 290;     // >= (FT+2)*LDT = 272, == 2 mod 32
 constexpr int WG_GPLANE = 130;     // >= FT*TT = 128, == 2 mod 32 (dy tile)
-constexpr int WG_CIMAX = 32;       // input channels staged per pass
 
 template <int CT, int JT>
 __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_mfma(
@@ -624,12 +623,6 @@ __global__ void wgrad_reduce(const double* __restrict__ partial, int nparts,
   }
 }
 
-constexpr int WG_BLOCKS = 512;
-constexpr int WG_GROUPS = 16;  // stage-1 groups of WG_BLOCKS/WG_GROUPS slabs
-
-static int wgrad_ct(int Cout) { return (Cout + 15) / 16; }
-static int wgrad_pass(int Cin) { return Cin < WG_CIMAX ? Cin : WG_CIMAX; }
-
 
 // ------------------------------------------------------------ small channels
 // Convolutions whose one side has 1-2 channels (the encoder's first conv
@@ -906,9 +899,8 @@ __global__ __launch_bounds__(256) void conv3x3_small_wgrad(
 // layer-0 GEMM pair on the side stream).  Rows are loaded SW_RB at a time.
 // Partial slabs: [tile][NOUT] with the old kernel's output order, reduced by
 // the same fixed-order wgrad_reduce1 + small_wgrad_final.
-constexpr int SW_RS = 32;          // rows per strip
-constexpr int SW_TW = 62;          // output columns per wave
-constexpr int SW_RB = 8;           // rows loaded per batch
+// (SW_RS rows per strip, SW_TW output columns per wave, SW_RB rows per batch:
+// conv_route.h)
 
 template <int CA, int CG, bool PRO>
 __global__ __launch_bounds__(256) void conv3x3_strip_wgrad(
@@ -1005,7 +997,6 @@ __global__ __launch_bounds__(256) void conv3x3_strip_wgrad(
 // pixels (columns t0-1 .. t0+14; lanes of pixels 1..14 own outputs) x 4
 // channel quads; the column shifts are lane shifts by 4.  ACL: act(x) is the
 // 16-channel side (16 -> 1 conv, dy one plane); else dy is (1 -> 16).
-constexpr int SWC_TW = 14;         // output columns per wave
 
 // Round 6, BNA (1 -> 16 only, !ACL): dy is not read but formed per element
 // from the BatchNorm+ReLU backward of the 16-channel layer -- g (the gradient
@@ -1213,8 +1204,6 @@ __global__ __launch_bounds__(256) void conv3x3_strip_wgrad_cl(
 // columns, (R1_RS+2)/R1_RS rows).  BatchNorm partials: one [sum y, sum y^2]
 // row per workgroup of four strips (fp32 per lane and wave, fp64 across
 // waves).  Another summation order than conv3x3_small_fwd (within 1e-6).
-constexpr int R1_TW = 14;   // output columns per wave
-constexpr int R1_RS = 16;   // rows per strip
 
 template <bool PRO>
 __global__ __launch_bounds__(256) void conv3x3_rows_16to1(
@@ -1341,8 +1330,6 @@ __global__ __launch_bounds__(256) void conv3x3_rows_16to1(
 // identical to it.  BatchNorm partials: one row per workgroup of four strips,
 // [sum | sum of squares] (forward) or [sum gz | sum gz * xhat] (Bnr) x 16
 // channels, lanes in fp32, workgroup in fp64 (<= exact_stat_parts rows).
-constexpr int R16_TW = 14;   // output columns per wave
-constexpr int R16_RS = 16;   // rows per strip
 
 // OUT (data gradient of Conv2d(16, 1) feeding a BatchNorm+ReLU, decoder.5 ->
 // decoder.6): 0 = store dx; 1 = store nothing (the fused reduce's partials
@@ -1513,25 +1500,12 @@ __global__ __launch_bounds__(256) void conv3x3_rows_1to16(
   }
 }
 
-// AINP_SMALL_ROWS=0: the 8 x 48 LDS tile kernel for the 16 -> 1 forward (A/B)
-static bool small_rows_env() {
-  static const bool v = [] {
-    const char* e = getenv("AINP_SMALL_ROWS");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-static int64_t rows16to1_strips(int64_t N, int64_t H, int64_t W) {
-  return N * cdiv(H, R1_RS) * cdiv(W, R1_TW);
-}
-
 // dw[o] (o < COUT*CIN*9, [co][ci][tap] order) and dbias from the group sums
 // first-stage groups of the small weight gradients' slab sum: their slabs are
 // only 145-160 floats wide, so WG_GROUPS (16) groups left one thread per
 // output summing 430 rows one after another (47 us at the C2 shape, on the
 // critical path at the end of the backward); 128 groups of ~54 rows
-constexpr int SWG_GROUPS = 128, SWG_GROUPS_MAX = 128;
+// (SWG_GROUPS, conv_route.h)
 
 __global__ __launch_bounds__(SWG_GROUPS_MAX) void small_wgrad_final(
     const double* __restrict__ tmp, int ngroups, int nw, int nout, float* __restrict__ dw,
@@ -1551,11 +1525,6 @@ __global__ __launch_bounds__(SWG_GROUPS_MAX) void small_wgrad_final(
     if (o < nw) dw[o] = (float)v;
     else if (dbias) dbias[o - nw] = (float)v;
   }
-}
-
-// (Cin, Cout) pairs with a dedicated small-channel kernel
-static bool small_pair(int a, int b) {
-  return ((a == 1 || a == 2) && b == 16) || ((b == 1 || b == 2) && a == 16);
 }
 
 template <int CIN, int COUT, bool XL, bool YL>
@@ -1590,50 +1559,39 @@ static void launch_small_fwd(bool dgrad, const float* x, const float* w, const f
   else launch_small_fwd_l<CIN, COUT, false, false>(dgrad, x, w, bias, sc, sh, y, stats, N, H, W, s, bnr);
 }
 
-// *used: the BatchNorm partial rows written (<= exact_stat_parts)
-static int small_fwd_dispatch(bool dgrad, const float* x, const float* w, const float* bias,
-                              const float* sc, const float* sh, float* y, double* stats,
-                              int64_t N, int Cin, int Cout, int64_t H, int64_t W, hipStream_t s,
-                              int lay = 0, const Bnr& bnr = Bnr{}, int64_t* used = nullptr) {
-  if (used) *used = N * cdiv(H, CV_FT) * cdiv(W, CV_TT);   // exact_stat_parts
-  // (the BatchNorm partial rows of a row-strip launch stay within
-  // exact_stat_parts; otherwise the tile kernel runs)
-  if (!dgrad && Cin == 16 && Cout == 1 && (lay & 1) && small_rows_env() &&
-      N * H * W * 16 < ((int64_t)1 << 40) && rows16to1_strips(N, H, W) < ((int64_t)1 << 31) &&
-      cdiv(rows16to1_strips(N, H, W), 4) <= N * cdiv(H, CV_FT) * cdiv(W, CV_TT)) {
+// the small-channel kernel the route chose (CK_ROWS_16TO1 / CK_ROWS_1TO16 /
+// CK_SMALL_TILE)
+static int small_fwd_launch(const ConvRoute& r, bool dgrad, const float* x, const float* w,
+                            const float* bias, const float* sc, const float* sh, float* y,
+                            double* stats, int64_t N, int Cin, int Cout, int64_t H, int64_t W,
+                            hipStream_t s, int lay, const Bnr& bnr) {
+  const dim3 grid((unsigned)r.gx);
+  if (r.kernel == CK_ROWS_16TO1) {
     const int nfs = (int)cdiv(H, R1_RS), nts = (int)cdiv(W, R1_TW);
-    const int64_t ns = rows16to1_strips(N, H, W), nb = cdiv(ns, 4);
-    if (used) *used = nb;
-    const dim3 grid((unsigned)nb);
+    const int ns = (int)(N * nfs * nts);
     if (sc)
       hipLaunchKernelGGL(conv3x3_rows_16to1<true>, grid, dim3(256), 0, s, x, w, bias, sc, sh, y,
-                         stats, (int)H, (int)W, nfs, nts, (int)ns);
+                         stats, (int)H, (int)W, nfs, nts, ns);
     else
       hipLaunchKernelGGL(conv3x3_rows_16to1<false>, grid, dim3(256), 0, s, x, w, bias, sc, sh, y,
-                         stats, (int)H, (int)W, nfs, nts, (int)ns);
+                         stats, (int)H, (int)W, nfs, nts, ns);
     return check_launch("conv3x3_rows_16to1");
   }
-  if (Cin == 1 && Cout == 16 && (lay & 2) && small_rows_env() &&
-      N * H * W * 16 < ((int64_t)1 << 40) && (dgrad || !bnr.y)) {
+  if (r.kernel == CK_ROWS_1TO16) {
     const int nfs = (int)cdiv(H, R16_RS), nts = (int)cdiv(W, R16_TW);
-    const int64_t ns = N * nfs * nts, nb = cdiv(ns, 4);
-    if (nb <= N * cdiv(H, CV_FT) * cdiv(W, CV_TT) && ns < ((int64_t)1 << 31)) {
-      if (used) *used = nb;
-      const bool fz = dgrad && bnr.y && stats;
+    const int ns = (int)(N * nfs * nts);
+    const bool fz = dgrad && bnr.y && stats;
 #define AINP_R16(DGV, PROV, FZV, ...)                                                              \
-  hipLaunchKernelGGL((conv3x3_rows_1to16<DGV, PROV, FZV, ##__VA_ARGS__>), dim3((unsigned)nb),      \
-                     dim3(256), 0, s, x, w, bias, sc, sh, y, stats, bnr, (int)H, (int)W, nfs, nts, \
-                     (int)ns)
-      if (dgrad && fz && !y) AINP_R16(true, false, true, 1);   // partials only (dx recomputed)
-      else if (dgrad && fz) AINP_R16(true, false, true);
-      else if (dgrad) AINP_R16(true, false, false);
-      else if (sc) AINP_R16(false, true, false);
-      else AINP_R16(false, false, false);
+  hipLaunchKernelGGL((conv3x3_rows_1to16<DGV, PROV, FZV, ##__VA_ARGS__>), grid, dim3(256), 0, s,   \
+                     x, w, bias, sc, sh, y, stats, bnr, (int)H, (int)W, nfs, nts, ns)
+    if (dgrad && fz && !y) AINP_R16(true, false, true, 1);   // partials only (dx recomputed)
+    else if (dgrad && fz) AINP_R16(true, false, true);
+    else if (dgrad) AINP_R16(true, false, false);
+    else if (sc) AINP_R16(false, true, false);
+    else AINP_R16(false, false, false);
 #undef AINP_R16
-      return check_launch("conv3x3_rows_1to16");
-    }
+    return check_launch("conv3x3_rows_1to16");
   }
-  if (!y) return record_msg("conv3x3: a partials-only data gradient needs the row-strip kernel");
 #define AINP_SF(A, B) \
   if (Cin == A && Cout == B) { launch_small_fwd<A, B>(dgrad, x, w, bias, sc, sh, y, stats, N, H, W, s, lay, bnr); return check_launch("conv3x3_small_fwd"); }
   AINP_SF(1, 16) AINP_SF(2, 16) AINP_SF(16, 1) AINP_SF(16, 2)
@@ -1641,46 +1599,27 @@ static int small_fwd_dispatch(bool dgrad, const float* x, const float* w, const 
   return record_msg("conv3x3: no small-channel kernel for this pair");
 }
 
-// AINP_SMALL_WGRAD_TILE=1: the 8x48-tile kernel for every small pair (A/B)
+// AINP_SMALL_WGRAD_TILE=1: the 8x48-tile kernel for every small pair (A/B;
+// read per call)
 static bool small_wgrad_tile_env() {
   const char* e = getenv("AINP_SMALL_WGRAD_TILE");
   return e && e[0] == '1';
 }
 
-
-static int64_t strip_tiles(int64_t N, int64_t H, int64_t W) {
-  return N * cdiv(H, SW_RS) * cdiv(W, SW_TW);
-}
-
-static size_t small_wgrad_ws(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
-  int64_t nblk = N * cdiv(H, CV_FT) * cdiv(W, CV_TT);
-  const int64_t ns = strip_tiles(N, H, W), nc = N * cdiv(H, SW_RS) * cdiv(W, SWC_TW);
-  if (ns > nblk) nblk = ns;
-  if (nc > nblk) nblk = nc;
-  const int nout = Cout * Cin * 9 + Cout;
-  return (size_t)nblk * nout * sizeof(float) + (size_t)SWG_GROUPS * nout * sizeof(double) + 16;
-}
-
-static int64_t strip_cl_tiles(int64_t N, int64_t H, int64_t W) {
-  return N * cdiv(H, SW_RS) * cdiv(W, SWC_TW);
-}
-
-// lay (round 5): bit 0 = x channel-last (its 16 channels: the 16 -> 1 conv),
-// bit 2 = dy channel-last (the 1 -> 16 conv); 1-channel tensors are the same
-// in both layouts
-static int small_wgrad(const float* x, const float* sc, const float* sh, const float* dy,
-                       float* dw, float* dbias, void* workspace, int64_t N, int Cin, int Cout,
-                       int64_t H, int64_t W, hipStream_t s, int lay = 0,
+// the small pairs' weight gradient on the kernel the route chose (WK_STRIP_CL:
+// the 16-channel side channel-last -- x of the 16 -> 1 conv, dy of the 1 -> 16
+// conv; 1-channel tensors are the same in both layouts), then the slab sum
+static int small_wgrad(const WgradRoute& r, const float* x, const float* sc, const float* sh,
+                       const float* dy, float* dw, float* dbias, void* workspace, int Cin,
+                       int Cout, int64_t H, int64_t W, hipStream_t s,
                        const BnApply* bna = nullptr) {
   const int nout = Cout * Cin * 9 + Cout;
   float* partial = reinterpret_cast<float*>(workspace);
-  int64_t nblk;
-  const bool acl = (lay & 1) && Cin == 16, gcl = (lay & 4) && Cout == 16;
-  if (bna && !(gcl && Cin == 1)) return record_msg("conv3x3_wgrad: fused BatchNorm apply: 1 -> 16 only");
-  if ((acl && Cout == 1) || (gcl && Cin == 1)) {
+  const int64_t nblk = r.slabs;
+  const dim3 grid((unsigned)r.gx, (unsigned)r.gy, (unsigned)r.gz);
+  if (r.kernel == WK_STRIP_CL) {
     const int ntf = (int)cdiv(H, SW_RS), ntt = (int)cdiv(W, SWC_TW);
-    nblk = strip_cl_tiles(N, H, W);
-    const dim3 grid((unsigned)cdiv(nblk, 4));
+    const bool acl = Cin == 16;
     if (bna && sc)
       hipLaunchKernelGGL((conv3x3_strip_wgrad_cl<false, true, true>), grid, dim3(256), 0, s, x, sc,
                          sh, dy, partial, (int)H, (int)W, ntf, ntt, (int)nblk, *bna);
@@ -1699,12 +1638,8 @@ static int small_wgrad(const float* x, const float* sc, const float* sh, const f
     else
       hipLaunchKernelGGL((conv3x3_strip_wgrad_cl<false, false>), grid, dim3(256), 0, s, x, sc, sh,
                          dy, partial, (int)H, (int)W, ntf, ntt, (int)nblk);
-  } else if (acl || gcl) {
-    return record_msg("conv3x3_wgrad: no channel-last small-channel kernel for this pair");
-  } else if (!small_wgrad_tile_env() && H * W < ((int64_t)1 << 31)) {
+  } else if (r.kernel == WK_STRIP) {
     const int ntf = (int)cdiv(H, SW_RS), ntt = (int)cdiv(W, SW_TW);
-    nblk = strip_tiles(N, H, W);
-    const dim3 grid((unsigned)nblk, (unsigned)cdiv(Cin * Cout, 4));
 #define AINP_SW(A, B) \
   else if (Cin == A && Cout == B && sc) hipLaunchKernelGGL((conv3x3_strip_wgrad<A, B, true>), grid, dim3(256), 0, s, x, sc, sh, dy, partial, (int)H, (int)W, ntf, ntt); \
   else if (Cin == A && Cout == B) hipLaunchKernelGGL((conv3x3_strip_wgrad<A, B, false>), grid, dim3(256), 0, s, x, sc, sh, dy, partial, (int)H, (int)W, ntf, ntt);
@@ -1713,8 +1648,6 @@ static int small_wgrad(const float* x, const float* sc, const float* sh, const f
     else return record_msg("conv3x3_wgrad: no small-channel kernel for this pair");
 #undef AINP_SW
   } else {
-    dim3 grid((unsigned)cdiv(W, CV_TT), (unsigned)cdiv(H, CV_FT), (unsigned)N);
-    nblk = (int64_t)grid.x * grid.y * grid.z;
 #define AINP_SW(A, B) \
   else if (Cin == A && Cout == B && sc) hipLaunchKernelGGL((conv3x3_small_wgrad<A, B, true>), grid, dim3(256), 0, s, x, sc, sh, dy, partial, (int)H, (int)W); \
   else if (Cin == A && Cout == B) hipLaunchKernelGGL((conv3x3_small_wgrad<A, B, false>), grid, dim3(256), 0, s, x, sc, sh, dy, partial, (int)H, (int)W);
@@ -1752,149 +1685,110 @@ static void launch_wgrad(const float* x, const float* sc, const float* sh,
 using namespace ainp;
 
 namespace ainp {
-int64_t conv_x6_stat_parts(int64_t N, int64_t H, int64_t W);
-int64_t conv_x6_stat_rows(bool dgrad, int Cin, int Cout, int64_t N, int64_t H, int64_t W,
-                          bool b16);
-bool conv_x6_dgrad16_ok(int Cin, int Cout, int64_t H, int64_t W);
-bool conv_x6_fwd16_ok(int Cin, int Cout, int64_t H, int64_t W);
-bool conv_x6_dgrad_cfnt_ok(int Cin, int Cout, int64_t N, int64_t H, int64_t W);
-int conv_wgrad_x6_launch(const float* x, const float* sc, const float* sh, const float* dy,
-                         float* partial, int64_t N, int Cin, int Cout, int64_t H, int64_t W,
-                         int ci0, int cp, int grid, hipStream_t s, bool b16, bool g16, bool x16,
-                         int lay, int* grid_used);
-int conv_x6_launch(bool dgrad, const float* x, const float* w, const float* bias,
-                   const float* sc, const float* sh, float* y, double* stats, int64_t N, int Cin,
-                   int Cout, int64_t H, int64_t W, hipStream_t s, int64_t* parts, bool b16,
-                   bool x16, bool y16, int lay, const Bnr* bnr = nullptr);
-
-// conv_x6.hip (fp32-accurate split-bf16 MFMA) serves every pair it has an
-// instantiation for unless AINP_CONV_EXACT=1 selects the exact f32 kernels.
-static bool conv_exact_env() {
-  static const bool v = [] {
-    const char* e = getenv("AINP_CONV_EXACT");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-
-static int64_t exact_stat_parts(int64_t N, int64_t H, int64_t W) {
-  return N * cdiv(H, CV_FT) * cdiv(W, CV_TT);
-}
+// conv_x6.hip: the split-bf16 kernels of a route (CK_X6P / CK_X6Q /
+// CK_X6_TILED / CK_FWD_B16DMA / CK_DGRAD_B16DMA; WK_X6S / WK_X6 / WK_B16DMA)
+int conv_x6_launch(const ConvRoute& r, bool dgrad, const float* x, const float* w,
+                   const float* bias, const float* sc, const float* sh, float* y, double* stats,
+                   int64_t N, int Cin, int Cout, int64_t H, int64_t W, hipStream_t s, bool b16,
+                   bool x16, bool y16, int lay, const Bnr& bnr);
+int conv_wgrad_x6_launch(const WgradRoute& r, const float* x, const float* sc, const float* sh,
+                         const float* dy, float* partial, int64_t N, int Cin, int Cout, int64_t H,
+                         int64_t W, int ci0, hipStream_t s, bool b16, bool g16, bool x16, int lay);
 }  // namespace ainp
 
-// Upper bound over both kernel families' tilings; the launch zero-fills the
-// partials its tiling does not produce, so the fixed-order sum is unchanged.
+// Host-only queries: each is what the routing of conv_route.h answers.
 extern "C" int ainp_conv3x3_fwd_stat_parts(int64_t N, int64_t H, int64_t W) {
-  const int64_t a = exact_stat_parts(N, H, W), b = conv_x6_stat_parts(N, H, W);
-  return (int)(a > b ? a : b);
+  return (int)conv_stat_parts(N, H, W);
 }
 
-// The BatchNorm partial rows ainp_conv3x3_fwd writes for this shape (the
-// kernel the dispatch below selects; fewer than the bound above when a
-// persistent kernel serves it).
+// The BatchNorm partial rows ainp_conv3x3_fwd writes for this shape (fewer
+// than the bound above when a persistent kernel serves it).
 extern "C" int64_t ainp_conv3x3_fwd_stat_rows_ex(int64_t N, int Cin, int Cout, int64_t H,
                                                  int64_t W, int flags) {
-  if (!small_pair(Cin, Cout) && !conv_exact_env()) {
-    const int64_t r =
-        conv_x6_stat_rows(false, Cin, Cout, N, H, W, (flags & AINP_CONV_BF16) != 0);
-    if (r) return r;
-  }
-  return exact_stat_parts(N, H, W);
+  return query_stat_rows(conv_env(), N, Cin, Cout, H, W, flags);
 }
 
 extern "C" int64_t ainp_conv3x3_fwd_stat_rows(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
   return ainp_conv3x3_fwd_stat_rows_ex(N, Cin, Cout, H, W, 0);
 }
 
+extern "C" int ainp_conv3x3_dgrad_cfnt_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
+  return query_dgrad_cfnt_ok(conv_env(), N, Cin, Cout, H, W) ? 1 : 0;
+}
+
+extern "C" int ainp_conv3x3_dy16_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
+  return query_dy16_ok(conv_env(), N, Cin, Cout, H, W) ? 1 : 0;
+}
+
+extern "C" int ainp_conv3x3_io16_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
+  return query_io16_ok(conv_env(), N, Cin, Cout, H, W) ? 1 : 0;
+}
+
+// Round 5: 1 if every conv3x3 entry point of this nn.Conv2d(Cin, Cout) takes
+// channel-last activations (AINP_CONV_XCL / _YCL / _GCL; host-only)
+extern "C" int ainp_conv3x3_cl_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
+  return query_cl_ok(conv_env(), N, Cin, Cout, H, W) ? 1 : 0;
+}
+
+// Round 6: 1 if ainp_conv3x3_dgrad_bnr with these flags takes dx == NULL (the
+// partials only; host-only)
+extern "C" int ainp_conv3x3_dgrad_bnr_nodx_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W,
+                                              int flags, int bn_flags) {
+  return query_dgrad_bnr_nodx_ok(conv_env(), N, Cin, Cout, H, W, flags, bn_flags) ? 1 : 0;
+}
+
 template <bool DG>
-static int conv_fwd_dispatch(const float* x, const float* w, const float* bias,
-                             const float* sc, const float* sh, float* y,
-                             double* stats, int64_t N, int Cin, int Cout,
-                             int64_t H, int64_t W, hipStream_t s, bool b16, bool x16 = false,
-                             bool y16 = false, int lay = 0) {
-  // partials [used, rows) of the BatchNorm statistics are zero
-  auto zero_tail = [&](int64_t used) -> int {
-    if (!stats) return AINP_OK;
-    const int64_t bound =
-        ainp_conv3x3_fwd_stat_rows_ex(N, Cin, Cout, H, W, b16 ? AINP_CONV_BF16 : 0);
-    if (used >= bound) return AINP_OK;
-    hipError_t e = hipMemsetAsync(stats + used * 2 * Cout, 0,
-                                  (size_t)(bound - used) * 2 * Cout * sizeof(double), s);
-    return e == hipSuccess ? AINP_OK : record_error(e, "conv3x3 stats tail");
-  };
-  static const char* kNo16 =
-      "conv3x3: bf16 storage (AINP_CONV_DY16 / _X16 / _Y16) needs a split-bf16 kernel for this pair";
-  if (small_pair(Cin, Cout)) {
-    if (x16 || y16) return record_msg(kNo16);
-    int64_t used = 0;
-    const int rc = small_fwd_dispatch(DG, x, w, bias, sc, sh, y, stats, N, Cin, Cout, H, W, s,
-                                      lay, Bnr{}, &used);
-    return rc ? rc : zero_tail(used);
-  }
-  if (!conv_exact_env()) {
-    int64_t parts = 0;
-    const int rc = conv_x6_launch(DG, x, w, bias, sc, sh, y, stats, N, Cin, Cout, H, W, s,
-                                  &parts, b16, x16, y16, lay);
-    if (rc == 2) return record_msg(lay ? "conv3x3: no channel-last / bf16-storage kernel for this pair"
-                                       : kNo16);
-    if (rc != 1) return rc ? rc : zero_tail(parts);
-  }
-  if (x16 || y16) return record_msg(kNo16);
-  if (lay) return record_msg("conv3x3: channel-last activations need a split-bf16 kernel for this pair");
-  {
-    const int rc = zero_tail(exact_stat_parts(N, H, W));
-    if (rc) return rc;
-  }
-  dim3 grid((unsigned)cdiv(W, CV_TT), (unsigned)cdiv(H, CV_FT), (unsigned)N);
-  const int ct = (Cout + 15) / 16;
-  const bool ex = Cin % CV_CK == 0 && Cout % 16 == 0 &&
-                  (int64_t)Cin * H * W * 4 < ((int64_t)1 << 31);
+static int exact_fwd_launch(const ConvRoute& r, const float* x, const float* w, const float* bias,
+                            const float* sc, const float* sh, float* y, double* stats, int Cin,
+                            int Cout, int64_t H, int64_t W, hipStream_t s) {
+  const dim3 grid((unsigned)r.gx, (unsigned)r.gy, (unsigned)r.gz);
 #define AINP_FWD(CTV)                                                                  \
   do {                                                                                 \
-    if (ex)                                                                            \
+    if (r.fast)                                                                        \
       hipLaunchKernelGGL((conv3x3_fwd_mfma<CTV, DG, true>), grid, dim3(256), 0, s, x, w, \
                          bias, sc, sh, y, stats, Cin, Cout, (int)H, (int)W);           \
     else                                                                               \
       hipLaunchKernelGGL((conv3x3_fwd_mfma<CTV, DG, false>), grid, dim3(256), 0, s, x, \
                          w, bias, sc, sh, y, stats, Cin, Cout, (int)H, (int)W);        \
   } while (0)
-  switch (ct) {
+  switch ((Cout + 15) / 16) {
     case 1: AINP_FWD(1); break;
     case 2: AINP_FWD(2); break;
     case 3: AINP_FWD(3); break;
-    case 4: AINP_FWD(4); break;
-    default: return record_msg("conv3x3: Cout > 64 unsupported");
+    default: AINP_FWD(4); break;
   }
 #undef AINP_FWD
   return check_launch("conv3x3_fwd_mfma");
 }
 
-static bool conv_flags_ok(int flags) { return (flags & ~AINP_CONV_BF16) == 0; }
-// forward: the act(x) source and / or y in bf16 storage (with the bf16 arithmetic);
-// either may be channel-last
-static bool conv_fwd_flags_ok(int flags) {
-  const int cl = flags & (AINP_CONV_XCL | AINP_CONV_YCL);
-  flags &= ~cl;
-  return (flags & ~(AINP_CONV_BF16 | AINP_CONV_X16 | AINP_CONV_Y16)) == 0 &&
-         (!(flags & (AINP_CONV_X16 | AINP_CONV_Y16)) || (flags & AINP_CONV_BF16));
-}
-// data / weight gradients: dy may be bf16 storage (with the bf16 arithmetic);
-// data gradient: dy / dx channel-last; weight gradient: x / dy channel-last
-static bool conv_grad_flags_ok(int flags, bool wgrad) {
-  // data gradient: dx [C][H][N][W] (AINP_CONV_YCFNT) instead of channel-last
-  if ((flags & AINP_CONV_YCFNT) && (wgrad || (flags & AINP_CONV_YCL))) return false;
-  if (!wgrad) flags &= ~AINP_CONV_YCFNT;
-  const int cl = flags & (wgrad ? (AINP_CONV_XCL | AINP_CONV_GCL) : (AINP_CONV_XCL | AINP_CONV_YCL));
-  flags &= ~cl;
-  const int extra = AINP_CONV_DY16 | (wgrad ? AINP_CONV_X16 : 0);
-  return (flags & ~(AINP_CONV_BF16 | extra)) == 0 &&
-         (!(flags & extra) || (flags & AINP_CONV_BF16));
-}
-// ABI layout flags -> the kernels' layout bits (bit 0 input, bit 1 output,
-// bit 2 the weight gradient's dy)
-static int conv_lay(int flags) {
-  return ((flags & AINP_CONV_XCL) ? 1 : 0) | ((flags & AINP_CONV_YCL) ? 2 : 0) |
-         ((flags & AINP_CONV_GCL) ? 4 : 0) | ((flags & AINP_CONV_YCFNT) ? 8 : 0);
+// One forward / data-gradient call on the kernel of its route; partials
+// [rows, rows_pad) of the BatchNorm statistics are zeroed.
+static int conv_launch(const ConvRoute& r, const ConvCall& c, const float* x, const float* w,
+                       const float* bias, const float* sc, const float* sh, float* y,
+                       double* stats, hipStream_t s, const Bnr& bnr = Bnr{}) {
+  if (!r.ok()) return record_msg(conv_refusal_text(r.refuse));
+  int rc;
+  switch (r.kernel) {
+    case CK_ROWS_16TO1:
+    case CK_ROWS_1TO16:
+    case CK_SMALL_TILE:
+      rc = small_fwd_launch(r, c.dgrad, x, w, bias, sc, sh, y, stats, c.N, c.Cin, c.Cout, c.H, c.W,
+                            s, c.lay, bnr);
+      break;
+    case CK_EXACT:
+      rc = c.dgrad ? exact_fwd_launch<true>(r, x, w, bias, sc, sh, y, stats, c.Cin, c.Cout, c.H,
+                                            c.W, s)
+                   : exact_fwd_launch<false>(r, x, w, bias, sc, sh, y, stats, c.Cin, c.Cout, c.H,
+                                             c.W, s);
+      break;
+    default:
+      rc = conv_x6_launch(r, c.dgrad, x, w, bias, sc, sh, y, stats, c.N, c.Cin, c.Cout, c.H, c.W,
+                          s, c.b16, c.x16, c.y16, c.lay, bnr);
+  }
+  if (rc || !stats || r.rows >= r.rows_pad) return rc;
+  hipError_t e = hipMemsetAsync(stats + r.rows * 2 * c.Cout, 0,
+                                (size_t)(r.rows_pad - r.rows) * 2 * c.Cout * sizeof(double), s);
+  return e == hipSuccess ? AINP_OK : record_error(e, "conv3x3 stats tail");
 }
 
 extern "C" int ainp_conv3x3_fwd_ex(const float* x, const float* w,
@@ -1908,10 +1802,12 @@ extern "C" int ainp_conv3x3_fwd_ex(const float* x, const float* w,
   if ((in_scale == nullptr) != (in_shift == nullptr))
     return record_msg("ainp_conv3x3_fwd: in_scale/in_shift must both be set");
   if (N == 0) return AINP_OK;
-  return conv_fwd_dispatch<false>(x, w, bias, in_scale, in_shift, y, stats, N,
-                                  Cin, Cout, H, W, as_stream(stream),
-                                  (flags & AINP_CONV_BF16) != 0, (flags & AINP_CONV_X16) != 0,
-                                  (flags & AINP_CONV_Y16) != 0, conv_lay(flags));
+  ConvCall c = conv_call(false, N, Cin, Cout, H, W, flags);
+  c.stats = stats != nullptr;
+  c.bias = bias != nullptr;
+  c.pro = in_scale != nullptr;
+  return conv_launch(route_conv(conv_env(), c), c, x, w, bias, in_scale, in_shift, y, stats,
+                     as_stream(stream));
 }
 
 extern "C" int ainp_conv3x3_fwd(const float* x, const float* w,
@@ -1931,20 +1827,12 @@ extern "C" int ainp_conv3x3_dgrad_ex(const float* dy, const float* w, float* dx,
   if (!dy || !w || !dx || N < 0 || Cin < 1 || Cout < 1 || H < 1 || W < 1 ||
       N > 65535 || !conv_grad_flags_ok(flags, false))
     return record_msg("ainp_conv3x3_dgrad: bad argument");
-  if ((flags & AINP_CONV_YCFNT) && ainp_conv3x3_dgrad_cfnt_ok(N, Cin, Cout, H, W) != 1)
-    return record_msg("ainp_conv3x3_dgrad: AINP_CONV_YCFNT serves the 32 -> 16 channel data "
-                      "gradient only (see ainp_conv3x3_dgrad_cfnt_ok)");
-  if (N == 0) return AINP_OK;
   // conv over dy (Cout channels) producing Cin channels, flipped weights
-  return conv_fwd_dispatch<true>(dy, w, nullptr, nullptr, nullptr, dx, nullptr,
-                                 N, Cout, Cin, H, W, as_stream(stream),
-                                 (flags & AINP_CONV_BF16) != 0, (flags & AINP_CONV_DY16) != 0,
-                                 false, conv_lay(flags));
-}
-
-extern "C" int ainp_conv3x3_dgrad_cfnt_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
-  if (N < 0 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || conv_exact_env()) return 0;
-  return conv_x6_dgrad_cfnt_ok(Cout, Cin, N, H, W) ? 1 : 0;
+  const ConvCall c = conv_call(true, N, Cin, Cout, H, W, flags);
+  const ConvRoute r = route_conv(conv_env(), c);
+  if (r.refuse == CR_CFNT) return record_msg(conv_refusal_text(CR_CFNT));
+  if (N == 0) return AINP_OK;
+  return conv_launch(r, c, dy, w, nullptr, nullptr, nullptr, dx, nullptr, as_stream(stream));
 }
 
 extern "C" int ainp_conv3x3_dgrad(const float* dy, const float* w, float* dx,
@@ -1958,25 +1846,13 @@ extern "C" int ainp_conv3x3_dgrad(const float* dy, const float* w, float* dx,
 // fused into its epilogue (conv_x6.hip Bnr): the split-bf16 data-gradient
 // kernels with a channel-last dx sum (gz, gz * xhat) of the value they just
 // computed into per-workgroup partials, so the separate reduce pass over dx
-// and y disappears.  Pairs without such a kernel run the data gradient and
-// then the channel-last reduce (same results, two passes).
-static bool dgrad_bnr_env() {
-  static const bool v = [] {
-    const char* e = getenv("AINP_DGRAD_BNR");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
+// and y disappears.  Pairs without such a kernel (ConvRoute::two_pass) run
+// the data gradient and then the channel-last reduce (same results).
 extern "C" int64_t ainp_conv3x3_dgrad_bnr_workspace(int64_t N, int Cin, int Cout, int64_t H,
                                                     int64_t W) {
   (void)Cout;
   if (N < 0 || Cin < 1 || H < 1 || W < 1) return 0;
-  int64_t rows = N * cdiv(H, 8) * cdiv(W, 32);            // 8-row tiles
-  const int64_t pers = 512 * (int64_t)X6_OCC_MAX;         // persistent grids
-  if (rows < pers) rows = pers;
-  if (rows < exact_stat_parts(N, H, W)) rows = exact_stat_parts(N, H, W);   // small convs
-  const int64_t fused = rows * 2 * Cin * (int64_t)sizeof(double);
+  const int64_t fused = sat_mul(dgrad_bnr_rows(N, H, W), 2 * Cin, (int64_t)sizeof(double));
   const int64_t sep = (int64_t)ainp_bn_relu_bwd_workspace(N, Cin, H, W);
   return fused > sep ? fused : sep;
 }
@@ -1987,41 +1863,26 @@ extern "C" int ainp_conv3x3_dgrad_bnr(const float* dy, const float* w, float* dx
                                       const float* save_mean_rstd, void* workspace, double* sums,
                                       int bn_flags, void* stream) {
   auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  if (!dy || !w || !y || !scale || !shift || !save_mean_rstd || !workspace || !sums ||
+      !dgrad_bnr_args_ok(N, Cin, Cout, H, W, flags, bn_flags) || !al16(dx) || !al16(y) ||
+      !al16(scale) || !al16(shift) || !al16(save_mean_rstd))
+    return record_msg(conv_refusal_text(CR_BNR_ARG));
   // dx == nullptr (round 6): the partials only, for the 1 -> 16 data gradient
   // whose dx the apply recomputes (ainp_conv3x3_dgrad_bnapply)
-  const bool nodx = !dx && small_pair(Cout, Cin) && Cin == 16 && dgrad_bnr_env() &&
-                    !(flags & AINP_CONV_DY16);
-  if (!dy || !w || (!dx && !nodx) || !y || !scale || !shift || !save_mean_rstd || !workspace ||
-      !sums || N < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || N > 65535 ||
-      !conv_grad_flags_ok(flags, false) || !(flags & AINP_CONV_YCL) ||
-      (bn_flags & ~AINP_BN_Y16) || !(Cin == 16 || Cin == 32 || Cin == 64) ||
-      !al16(dx) || !al16(y) || !al16(scale) || !al16(shift) || !al16(save_mean_rstd))
-    return record_msg("ainp_conv3x3_dgrad_bnr: bad argument (channel-last dx and y, C in "
-                      "{16, 32, 64}, 16-byte aligned dx / y / scale / shift / save)");
+  const ConvCall c = dgrad_bnr_call(N, Cin, Cout, H, W, flags, bn_flags, dx == nullptr);
+  const ConvRoute r = route_conv(conv_env(), c);
   const hipStream_t s = as_stream(stream);
+  if (r.two_pass) {
+    const int rc = conv_launch(r, c, dy, w, nullptr, nullptr, nullptr, dx, nullptr, s);
+    if (rc) return rc;
+    return ainp_bn_relu_bwd_reduce_ex(dx, reinterpret_cast<const float*>(y), scale, shift,
+                                      save_mean_rstd, workspace, sums, N, Cin, H, W, 0,
+                                      AINP_BN_CL | (bn_flags & AINP_BN_Y16), stream);
+  }
   const Bnr bnr{y, scale, shift, save_mean_rstd, (bn_flags & AINP_BN_Y16) ? 1 : 0};
   double* partial = reinterpret_cast<double*>(workspace);
-  if (dgrad_bnr_env() && small_pair(Cout, Cin) && Cin % 4 == 0 && !(flags & AINP_CONV_DY16)) {
-    // 1 -> 16 channels: the small kernel's channel-last epilogue
-    int64_t used = 0;
-    const int rc = small_fwd_dispatch(true, dy, w, nullptr, nullptr, nullptr, dx, partial, N,
-                                      Cout, Cin, H, W, s, conv_lay(flags), bnr, &used);
-    if (rc) return rc;
-    return bn_cl_sum_partials(partial, (int)used, 2 * Cin, sums, s);
-  }
-  if (dgrad_bnr_env() && !small_pair(Cout, Cin) && !conv_exact_env()) {
-    int64_t parts = 0;
-    const int rc = conv_x6_launch(true, dy, w, nullptr, nullptr, nullptr, dx, partial, N, Cout,
-                                  Cin, H, W, s, &parts, (flags & AINP_CONV_BF16) != 0,
-                                  (flags & AINP_CONV_DY16) != 0, false, conv_lay(flags), &bnr);
-    if (rc == AINP_OK) return bn_cl_sum_partials(partial, (int)parts, 2 * Cin, sums, s);
-    if (rc < 0) return rc;
-  }
-  const int rc = ainp_conv3x3_dgrad_ex(dy, w, dx, nullptr, N, Cin, Cout, H, W, flags, stream);
-  if (rc) return rc;
-  return ainp_bn_relu_bwd_reduce_ex(dx, reinterpret_cast<const float*>(y), scale, shift,
-                                    save_mean_rstd, workspace, sums, N, Cin, H, W, 0,
-                                    AINP_BN_CL | (bn_flags & AINP_BN_Y16), stream);
+  const int rc = conv_launch(r, c, dy, w, nullptr, nullptr, nullptr, dx, partial, s, bnr);
+  return rc ? rc : bn_cl_sum_partials(partial, (int)r.rows, 2 * Cin, sums, s);
 }
 
 // Round 6: Conv2d(16, 1)'s data gradient (dy one channel -> dx 16, decoder.6)
@@ -2035,13 +1896,13 @@ extern "C" int ainp_conv3x3_dgrad_bnapply(const float* dy, const float* w, const
                                           float* dgamma, float* dbeta, int64_t N, int Cin,
                                           int Cout, int64_t H, int64_t W, void* stream) {
   auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  const int nfs = (int)cdiv(H > 0 ? H : 1, R16_RS), nts = (int)cdiv(W > 0 ? W : 1, R16_TW);
-  const int64_t ns = N * nfs * nts;
   if (!dy || !w || !y || !scale || !shift || !save_mean_rstd || !sums || !gy || N < 1 || H < 1 ||
       W < 1 || Cin != 16 || Cout != 1 || count < 0 || !al16(y) || !al16(gy) ||
-      ns >= ((int64_t)1 << 31) || N * H * W * 16 >= ((int64_t)1 << 40))
+      tiles(N, H, W, R16_RS, R16_TW) >= LIM_OFF32 || !below(LIM_ELEM40, N, H, W, 16))
     return record_msg("ainp_conv3x3_dgrad_bnapply: bad argument (Conv2d(16, 1), channel-last "
                       "16-byte aligned fp32 y, gy)");
+  const int nfs = (int)cdiv(H, R16_RS), nts = (int)cdiv(W, R16_TW);
+  const int64_t ns = N * nfs * nts;
   const Bnr bnr{y, scale, shift, save_mean_rstd, 0};
   const BnApply bna{nullptr, y, scale, shift, gamma, save_mean_rstd, sums, dgamma, dbeta,
                     count > 0 ? 1.0 / (double)count : 0.0};
@@ -2059,60 +1920,9 @@ extern "C" int ainp_conv3x3_dgrad_bnapply(const float* dy, const float* w, const
   return check_launch("conv3x3_rows_1to16 (apply)");
 }
 
-extern "C" int ainp_conv3x3_dy16_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
-  (void)N;
-  if (Cin < 1 || Cout < 1 || H < 1 || W < 1 || small_pair(Cin, Cout) || conv_exact_env())
-    return 0;
-  // weight gradient: one 32-channel pass on conv3x3_wgrad_x6(s) (conv_wgrad_x6_launch)
-  const bool fits =
-      (int64_t)H * W * 4 * (Cout > WG_CIMAX ? Cout : WG_CIMAX) < ((int64_t)1 << 31);
-  const int cp = wgrad_pass(Cin);
-  if (!fits || Cin > WG_CIMAX ||
-      !((cp == 32 && Cout == 16) || (cp == 16 && Cout == 32) || (cp == 32 && Cout == 64)))
-    return 0;
-  // data gradient: the conv over dy (Cout channels) producing Cin
-  return conv_x6_dgrad16_ok(Cout, Cin, H, W) ? 1 : 0;
-}
-
-extern "C" int ainp_conv3x3_io16_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
-  (void)N;
-  if (Cin < 1 || Cout < 1 || H < 1 || W < 1 || small_pair(Cin, Cout) || conv_exact_env())
-    return 0;
-  const bool fits =
-      (int64_t)H * W * 4 * (Cout > WG_CIMAX ? Cout : WG_CIMAX) < ((int64_t)1 << 31);
-  const int cp = wgrad_pass(Cin);
-  if (!fits || Cin > WG_CIMAX ||
-      !((cp == 32 && Cout == 16) || (cp == 16 && Cout == 32) || (cp == 32 && Cout == 64)))
-    return 0;
-  return conv_x6_fwd16_ok(Cin, Cout, H, W) ? 1 : 0;
-}
-
-// Round 5: 1 if every conv3x3 entry point of this nn.Conv2d(Cin, Cout) takes
-// channel-last activations (AINP_CONV_XCL / _YCL / _GCL; host-only)
-extern "C" int ainp_conv3x3_cl_ok(int64_t N, int Cin, int Cout, int64_t H, int64_t W) {
-  (void)N;
-  if (Cin < 1 || Cout < 1 || H < 1 || W < 1 || conv_exact_env()) return 0;
-  const int64_t cmax = Cin > Cout ? Cin : Cout;
-  if (H * W * cmax * 4 >= ((int64_t)1 << 31)) return 0;
-  if (small_pair(Cin, Cout)) return (Cin == 16 && Cout == 1) || (Cin == 1 && Cout == 16);
-  // forward (persistent x6p / x6q), data gradient (x6p / x6q / 8-row tiled),
-  // weight gradient (one 32-channel pass on wgrad_x6 / x6s)
-  const bool fwd = (Cin == 16 && Cout == 32) || (Cin == 32 && Cout == 64) ||
-                   (Cin == 32 && Cout == 16);
-  const bool dgr = (Cout == 32 && Cin == 16) || (Cout == 16 && Cin == 32) ||
-                   (Cout == 64 && Cin == 32);
-  return fwd && dgr ? 1 : 0;
-}
-
 extern "C" size_t ainp_conv3x3_wgrad_workspace(int64_t N, int Cin, int Cout,
                                                int64_t H, int64_t W) {
-  if (small_pair(Cin, Cout)) return small_wgrad_ws(N, Cin, Cout, H, W);
-  const int cp = wgrad_pass(Cin);
-  int ct = wgrad_ct(Cout);
-  if (ct == 3) ct = 4;
-  // slabs for the largest grid (the bf16 x6 kernels' multiplier, conv_x6_occ16)
-  return (size_t)(WG_BLOCKS * X6_OCC_MAX + 2 * WG_GROUPS) * ct * 16 * (9 * cp + 1) *
-         sizeof(float);
+  return wgrad_workspace_bytes(N, Cin, Cout, H, W);
 }
 
 extern "C" int ainp_conv3x3_wgrad(const float* x, const float* in_scale,
@@ -2143,8 +1953,23 @@ extern "C" int ainp_conv3x3_wgrad_bnapply(const float* x, const float* in_scale,
                       "16-byte aligned fp32 g / y)");
   const BnApply bna{g, y, scale, shift, gamma, save_mean_rstd, sums, dgamma, dbeta,
                     count > 0 ? 1.0 / (double)count : 0.0};
-  return small_wgrad(x, in_scale, in_shift, nullptr, dw, dbias, workspace, N, Cin, Cout, H, W,
-                     as_stream(stream), 4, &bna);
+  WgradCall c = wgrad_call(N, Cin, Cout, H, W, AINP_CONV_GCL);
+  c.bna = true;
+  const WgradRoute r = route_wgrad(conv_env(), c);
+  if (!r.ok()) return record_msg(conv_refusal_text(r.refuse));
+  return small_wgrad(r, x, in_scale, in_shift, nullptr, dw, dbias, workspace, Cin, Cout, H, W,
+                     as_stream(stream), &bna);
+}
+
+// compute units of the current device (WK_B16DMA runs one workgroup on each)
+static int device_cus() {
+  static const int v = [] {
+    int dev = 0, ncu = 256;
+    if (hipGetDevice(&dev) == hipSuccess)
+      (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    return ncu;
+  }();
+  return v;
 }
 
 extern "C" int ainp_conv3x3_wgrad_ex(const float* x, const float* in_scale,
@@ -2154,29 +1979,50 @@ extern "C" int ainp_conv3x3_wgrad_ex(const float* x, const float* in_scale,
                                      int64_t W, int flags, void* stream) {
   if (!x || !dy || !dw || !workspace || N < 1 || Cin < 1 || Cout < 1 ||
       H < 1 || W < 1 || !conv_grad_flags_ok(flags, true))
-    return record_msg("ainp_conv3x3_wgrad: bad argument");
-  const bool b16 = (flags & AINP_CONV_BF16) != 0;
-  const bool g16 = (flags & AINP_CONV_DY16) != 0;
-  const bool x16 = (flags & AINP_CONV_X16) != 0;
-  static const char* kNo16 =
-      "ainp_conv3x3_wgrad: bf16 storage (AINP_CONV_DY16 / _X16) needs a split-bf16 "
-      "weight-gradient kernel for this pair";
+    return record_msg(conv_refusal_text(CR_W_ARG));
   if ((in_scale == nullptr) != (in_shift == nullptr))
     return record_msg("ainp_conv3x3_wgrad: in_scale/in_shift must both be set");
-  const int lay = conv_lay(flags);
-  if (small_pair(Cin, Cout)) {
-    if (g16 || x16) return record_msg(kNo16);
-    return small_wgrad(x, in_scale, in_shift, dy, dw, dbias, workspace, N, Cin, Cout, H, W,
-                       as_stream(stream), lay);
-  }
-  const int CT = wgrad_ct(Cout);
-  if (CT > 4) return record_msg("ainp_conv3x3_wgrad: Cout > 64 unsupported");
-  const int CTp = CT == 3 ? 4 : CT;  // kernel co-tiles (waves split evenly)
+  WgradCall c = wgrad_call(N, Cin, Cout, H, W, flags);
+  c.small_tile = small_wgrad_tile_env();
+  if (c.g16 && c.x16) c.ncu = device_cus();   // bf16 storage on both sides: WK_B16DMA's grid
   hipStream_t s = as_stream(stream);
   float* partial = reinterpret_cast<float*>(workspace);
+  const int CTp = wgrad_ct(Cout) == 3 ? 4 : wgrad_ct(Cout);  // kernel co-tiles (waves split evenly)
   for (int ci0 = 0; ci0 < Cin; ci0 += WG_CIMAX) {
-    const int cp = (Cin - ci0) < WG_CIMAX ? (Cin - ci0) : WG_CIMAX;
-    const int JT = (9 * cp + 15) / 16;  // 1..18
+    c.ci0 = ci0;
+    const WgradRoute r = route_wgrad(conv_env(), c);
+    if (!r.ok()) return record_msg(conv_refusal_text(r.refuse));
+    const int cp = r.cp;
+    int rc;
+    switch (r.kernel) {
+      case WK_STRIP_CL:
+      case WK_STRIP:
+      case WK_SMALL_TILE:
+        return small_wgrad(r, x, in_scale, in_shift, dy, dw, dbias, workspace, Cin, Cout, H, W, s);
+      case WK_X6S:
+      case WK_X6:
+      case WK_B16DMA:
+        rc = conv_wgrad_x6_launch(r, x, in_scale, in_shift, dy, partial, N, Cin, Cout, H, W, ci0,
+                                  s, c.b16, c.g16, c.x16, c.lay);
+        break;
+      case WK_T:
+#define AINP_WGT(CPV, COV)                                                           \
+  hipLaunchKernelGGL((conv3x3_wgrad_t<CPV, COV>), dim3(WG_BLOCKS),                    \
+                     dim3(WgradT<CPV, COV>::NW * 64), 0, s, x,                          \
+                     in_scale, in_shift, dy, partial, (int)N, Cin, (int)H, (int)W, ci0)
+        switch (cp * 100 + Cout) {
+          case 1616: AINP_WGT(16, 16); break;
+          case 1632: AINP_WGT(16, 32); break;
+          case 1664: AINP_WGT(16, 64); break;
+          case 3216: AINP_WGT(32, 16); break;
+          case 3232: AINP_WGT(32, 32); break;
+          default: AINP_WGT(32, 64); break;
+        }
+#undef AINP_WGT
+        rc = check_launch("conv3x3_wgrad_mfma");
+        break;
+      default: {
+        const int JT = (9 * cp + 15) / 16;  // 1..18
 #define AINP_WG(CTV)                                                                \
   do {                                                                              \
     if (JT <= 1) launch_wgrad<CTV, 1>(x, in_scale, in_shift, dy, partial, (int)N,  \
@@ -2190,42 +2036,17 @@ extern "C" int ainp_conv3x3_wgrad_ex(const float* x, const float* in_scale,
     else launch_wgrad<CTV, 18>(x, in_scale, in_shift, dy, partial, (int)N, Cin,    \
                                Cout, (int)H, (int)W, ci0, cp, s);                   \
   } while (0)
-    // specialised kernel: 32-bit buffer offsets must cover a sample's planes
-    const bool fits = (int64_t)H * W * 4 * (Cout > WG_CIMAX ? Cout : WG_CIMAX) < ((int64_t)1 << 31);
-    const int key = fits ? cp * 100 + Cout : 0;
-#define AINP_WGT(CPV, COV)                                                           \
-  hipLaunchKernelGGL((conv3x3_wgrad_t<CPV, COV>), dim3(WG_BLOCKS),                    \
-                     dim3(WgradT<CPV, COV>::NW * 64), 0, s, x,                          \
-                     in_scale, in_shift, dy, partial, (int)N, Cin, (int)H, (int)W, ci0)
-    // split-bf16 kernel where it is instantiated (conv_x6.hip), unless
-    // AINP_CONV_EXACT=1; same slab format
-    int nblk_x6 = b16 ? WG_BLOCKS * conv_x6_occ16() : WG_BLOCKS;
-    int rc = (fits && !conv_exact_env())
-                 ? conv_wgrad_x6_launch(x, in_scale, in_shift, dy, partial, N, Cin, Cout, H, W,
-                                        ci0, cp, nblk_x6, s, b16, g16, x16, lay, &nblk_x6)
-                 : 1;
-    if (rc == 1 && (g16 || x16)) return record_msg(kNo16);
-    if (rc == 1 && lay)
-      return record_msg("ainp_conv3x3_wgrad: channel-last activations need a split-bf16 kernel");
-    const int nblk = rc == 0 ? nblk_x6 : WG_BLOCKS;   // slabs the launch writes
-    if (rc == 1) switch (key) {
-      case 1616: AINP_WGT(16, 16); break;
-      case 1632: AINP_WGT(16, 32); break;
-      case 1664: AINP_WGT(16, 64); break;
-      case 3216: AINP_WGT(32, 16); break;
-      case 3232: AINP_WGT(32, 32); break;
-      case 3264: AINP_WGT(32, 64); break;
-      default:
         switch (CTp) {
           case 1: AINP_WG(1); break;
           case 2: AINP_WG(2); break;
           default: AINP_WG(4); break;
         }
-    }
-#undef AINP_WGT
 #undef AINP_WG
-    if (rc == 1) rc = check_launch("conv3x3_wgrad_mfma");
+        rc = check_launch("conv3x3_wgrad_mfma");
+      }
+    }
     if (rc) return rc;
+    const int nblk = (int)r.slabs;   // slabs the launch wrote
     const int J = 9 * cp;
     const int per = CTp * 16 * (J + 1);
     double* tmp = reinterpret_cast<double*>(partial + (size_t)nblk * per);

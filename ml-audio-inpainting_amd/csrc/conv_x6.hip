@@ -26,13 +26,13 @@
 //    each output channel for the following BatchNorm (fp64, fixed order).
 // dgrad is the same kernel over dy with w'[ci][co][tap] = w[co][ci][8 - tap].
 #include "common.h"
+#include "conv_route.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace ainp {
 
-namespace cx6 {
-constexpr int TR = 16, TC = 32;          // output rows x columns per workgroup
+namespace cx6 {   // (TR x TC = 16 x 32 output rows x columns per workgroup: conv_route.h)
 constexpr int HR = TR + 2, HC = TC + 2;  // halo tile
 constexpr int CK = 16;                   // input channels per K chunk
 constexpr int XROW = HC * 32;            // bytes per halo row per piece (16 bf16 / pixel)
@@ -44,13 +44,6 @@ constexpr int XI = (XU + NT - 1) / NT;   // units per thread (3)
 }  // namespace cx6
 
 typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
-
-// activation layouts of a launch (bitmask): input / output / dy channel-last
-constexpr int CL_X = 1, CL_Y = 2, CL_G = 4;
-// round 6: a data gradient's dx written [C][H][N][W] (AINP_CONV_YCFNT) -- the
-// [C*F, N*T] operand of the fp32 output projection's backward GEMMs, so the
-// transposing copy of the decoder input gradient disappears (x6q only)
-constexpr int CL_CF = 8;
 
 __device__ __forceinline__ int wx6_clamp(int v, int lo, int hi) {
   return v < lo ? lo : (v > hi ? hi : v);
@@ -218,18 +211,7 @@ __device__ __forceinline__ bf16x8c cx6_ld(const unsigned char* p) {
 // tile i's 36 MFMA steps run.  Same LDS image layout (per 16-channel plane:
 // [row][col][16], halves swizzled by column bit 3), same weights image, same
 // chunk -> tap MFMA order as the register-staged kernel: bit-identical.
-namespace cdd {
-constexpr int CI = 64, COP = 32, TR = 8, TC = 32, HR = TR + 2, HC = TC + 2;
-constexpr int XROW = HC * 32, XPLANE = HR * XROW;           // 1088, 10880
-constexpr int NPIX = HR * HC;                                // 340 halo pixels
-constexpr int XBLK = (NPIX * 32 + 1023) / 1024;              // 11 DMA blocks per plane
-constexpr int XPP = XBLK * 1024;                             // padded plane
-constexpr int NCK = CI / 16;                                 // 4 planes
-constexpr int XBUF = NCK * XPP;                              // 45056 per halo buffer
-constexpr int WROW = 9 * 32 + 16, WPLANE = COP * WROW;       // 304, 9728
-constexpr int NT = 512;
-constexpr int YBLK = TR * TC * COP * 2 / 1024;              // 16 blocks: bf16 y of a tile
-}  // namespace cdd
+// (namespace cdd, the kernel's tile and LDS geometry: conv_route.h)
 __device__ __attribute__((aligned(64))) uint16_t cdd_zero[8];   // zero-initialised
 
 // global_load_lds_dwordx4 issued from inline asm (the recipe of
@@ -251,7 +233,8 @@ __device__ __forceinline__ void glds16_asm(const void* gsrc, const unsigned char
 // WREG (round 6): the wave's 36 weight fragments held in VGPRs (144) for the
 // whole kernel instead of re-read from LDS per tile -- half the LDS read
 // traffic of the MFMA loop (the LDS, 162 KB, allows one workgroup per CU
-// either way)
+// either way).  Only WREG = true is instantiated; the parameter stays so the
+// kernel keeps its name in profiles.
 template <bool WREG>
 __global__ __launch_bounds__(cdd::NT, WREG ? 1 : 2) void conv3x3_dgrad_b16dma_kernel(
     const uint16_t* __restrict__ gy, const float* __restrict__ w, float* __restrict__ dx,
@@ -421,8 +404,8 @@ __global__ __launch_bounds__(cdd::NT, WREG ? 1 : 2) void conv3x3_dgrad_b16dma_ke
 // NP = 1, G16, Y16, XL, YL>.  (The DMA is issued from inline asm, so hipcc
 // adds no vmcnt(0) before the LDS reads; the loop's own vmcnt(0) at the top
 // retires the tile's DMA and the previous epilogue's stores.)
-namespace cdf {
-constexpr int TR = 8, TC = 32, HR = TR + 2, HC = TC + 2;
+namespace cdf {   // (TR x TC = 8 x 32: conv_route.h)
+constexpr int HR = TR + 2, HC = TC + 2;
 constexpr int XROW = HC * 32;                                // 1088
 constexpr int NPIX = HR * HC;                                // 340 halo pixels
 constexpr int XBLK = (NPIX * 32 + 1023) / 1024;              // 11 DMA blocks per plane
@@ -686,24 +669,6 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_fwd_b16dma_kernel(
     stats[(int64_t)blockIdx.x * 2 * Cout + co] = sm;
     stats[(int64_t)blockIdx.x * 2 * Cout + Cout + co] = sq;
   }
-}
-
-// AINP_CONV16_DMA=0: the register-staged x6p forwards (A/B)
-static bool conv16_dma() {
-  static const bool v = [] {
-    const char* e = getenv("AINP_CONV16_DMA");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-// AINP_DGRAD16_DMA=0: the register-staged kernel for that data gradient (A/B)
-static bool dgrad16_dma() {
-  static const bool v = [] {
-    const char* e = getenv("AINP_DGRAD16_DMA");
-    return !(e && e[0] == '0');
-  }();
-  return v;
 }
 
 // RPW output rows per wave: 2 (16-row tiles, one workgroup per CU) or 1
@@ -985,89 +950,6 @@ __global__ __launch_bounds__(cx6::NT, RPW == 1 ? 4 : 2) void conv3x3_x6_kernel(
   }
 }
 
-// Upper bound on the BatchNorm partials an x6 launch writes for [N, H, W]
-// outputs: one per workgroup of the persistent kernel (<= 512), one per tile
-// of the tiled kernel.
-int64_t conv_x6_stat_parts(int64_t N, int64_t H, int64_t W) {
-  const int64_t tiled = N * cdiv(H, cx6::TR) * cdiv(W, cx6::TC);
-  return tiled > 512 ? tiled : 512;
-}
-
-int conv_x6p_launch(bool dgrad, const float* x, const float* w, const float* bias,
-                    const float* sc, const float* sh, float* y, double* stats, int64_t N, int Cin,
-                    int Cout, int64_t H, int64_t W, hipStream_t s, int64_t* parts, bool b16,
-                    bool x16, bool y16, int lay, const Bnr& bnr);
-
-// Persistent-grid multiplier of the bf16 (NP = 1) kernels: their LDS (21-50
-// KB) and VGPR (48-80) footprints let 2-4x the fp32 kernels' workgroups stay
-// resident, and they are bound by the loads a CU keeps in flight (SQ passes:
-// MFMA busy 0.05-0.10, waves parked on s_waitcnt 0.5-0.67 of their cycles,
-// profiles/r04e_*).  AINP_X6_OCC16 overrides (1 .. X6_OCC_MAX).
-int conv_x6_occ16() {
-  static const int v = [] {
-    const char* e = getenv("AINP_X6_OCC16");
-    const int o = e ? atoi(e) : 1;
-    return o < 1 ? 1 : (o > X6_OCC_MAX ? X6_OCC_MAX : o);
-  }();
-  return v;
-}
-
-// Launch if (Cin, Cout) has an x6 instantiation; returns 1 if not handled.
-// *parts = the number of BatchNorm partials written.  The persistent kernel
-// serves every pair it has (32-bit buffer offsets permitting); the tiled one
-// is kept for AINP_CONV_X6_TILED=1.
-// BatchNorm partial rows the x6 launch below writes for this shape (0: no x6
-// kernel serves it); mirrors conv_x6_launch / conv_x6p_launch.
-int64_t conv_x6_stat_rows(bool dgrad, int Cin, int Cout, int64_t N, int64_t H, int64_t W,
-                          bool b16) {
-  const int occ = b16 ? conv_x6_occ16() : 1;
-  if (Cout > 64 || Cout < 16) return 0;
-  const int cop = Cout <= 32 ? 32 : 64;
-  static const bool tiled_env = getenv("AINP_CONV_X6_TILED") != nullptr;
-  if (!tiled_env && (int64_t)(Cin > Cout ? Cin : Cout) * H * W * 4 < ((int64_t)1 << 31)) {
-    // one row per persistent workgroup (bf16: the multiplied grid)
-    if (!dgrad && Cin == 32 && cop == 64) return 256 * occ;
-    if (Cin == 16 && cop == 32) return 512 * occ;
-    if (Cin == 32 && Cout == 16) return 512 * occ;
-  }
-  if (((Cin == 32 && cop == 64) || (Cin == 64 && cop == 32)) &&
-      (int64_t)Cin * H * W * 4 < ((int64_t)1 << 31))    // 32-bit buffer offsets
-    return N * cdiv(H, cx6::TR) * cdiv(W, cx6::TC);
-  return 0;
-}
-
-// 1 if conv_x6_launch(dgrad = true, stats = nullptr, b16, x16) takes bf16 dy
-// for this (dy channels, dx channels) pair; mirrors its routing.
-bool conv_x6_dgrad16_ok(int Cin, int Cout, int64_t H, int64_t W) {
-  const int cop = Cout <= 32 ? 32 : 64;
-  static const bool tiled_env = getenv("AINP_CONV_X6_TILED") != nullptr;
-  if (Cout > 64 || Cout < 16) return false;
-  if (!tiled_env && (int64_t)(Cin > Cout ? Cin : Cout) * H * W * 4 < ((int64_t)1 << 31) &&
-      ((Cin == 16 && cop == 32) || (Cin == 32 && Cout == 16)))
-    return true;   // persistent x6p / x6q
-  return ((Cin == 32 && cop == 64) || (Cin == 64 && cop == 32)) &&
-         (int64_t)Cin * H * W * 4 < ((int64_t)1 << 31);   // tiled, 8-row tiles
-}
-
-// 1 if conv_x6_launch(dgrad = true, lay with CL_CF) serves this (dy channels,
-// dx channels) pair: the persistent 32 -> 16 data gradient (x6q)
-bool conv_x6_dgrad_cfnt_ok(int Cin, int Cout, int64_t N, int64_t H, int64_t W) {
-  static const bool tiled_env = getenv("AINP_CONV_X6_TILED") != nullptr;
-  return !tiled_env && Cin == 32 && Cout == 16 && N * H * W * 16 < ((int64_t)1 << 40) &&
-         (int64_t)Cin * H * W * 4 < ((int64_t)1 << 31);
-}
-
-// 1 if conv_x6_launch(dgrad = false, b16) serves this pair on a persistent
-// kernel, the only forwards with bf16-storage input / output (x16 / y16)
-bool conv_x6_fwd16_ok(int Cin, int Cout, int64_t H, int64_t W) {
-  const int cop = Cout <= 32 ? 32 : 64;
-  static const bool tiled_env = getenv("AINP_CONV_X6_TILED") != nullptr;
-  if (Cout > 64 || Cout < 16 || tiled_env ||
-      (int64_t)(Cin > Cout ? Cin : Cout) * H * W * 4 >= ((int64_t)1 << 31))
-    return false;
-  return (Cin == 32 && cop == 64) || (Cin == 16 && cop == 32) || (Cin == 32 && Cout == 16);
-}
-
 // Instantiate f for the run-time layout bits: f(xl, yl) with integral-constant
 // booleans (input / output channel-last)
 template <typename F>
@@ -1078,66 +960,36 @@ static void cl_dispatch(int lay, F&& f) {
   else f(std::false_type{}, std::false_type{});
 }
 
-int conv_x6_launch(bool dgrad, const float* x, const float* w, const float* bias,
-                   const float* sc, const float* sh, float* y, double* stats, int64_t N, int Cin,
-                   int Cout, int64_t H, int64_t W, hipStream_t s, int64_t* parts, bool b16,
-                   bool x16, bool y16, int lay, const Bnr* bnrp) {
-  const Bnr bnr = bnrp ? *bnrp : Bnr{};
-  // fused BatchNorm-backward reduce: a data gradient writing channel-last dx,
-  // whose partials are the (sum gz, sum gz * xhat) rows
-  const bool fused = bnr.y != nullptr;
-  // (dx of at most 32 channels: the fused instances)
-  if (fused && !(dgrad && stats && (lay & CL_Y) && !bias && Cout <= 32)) return 2;
-  if (conv_x6_stat_rows(dgrad, Cin, Cout, N, H, W, b16) == 0) return (lay & CL_CF) ? 2 : 1;
-  static const bool tiled_env = getenv("AINP_CONV_X6_TILED") != nullptr;
-  if (!tiled_env && (int64_t)(Cin > Cout ? Cin : Cout) * H * W * 4 < ((int64_t)1 << 31)) {
-    const int rc = conv_x6p_launch(dgrad, x, w, bias, sc, sh, y, stats, N, Cin, Cout, H, W, s,
-                                   parts, b16, x16, y16, lay, bnr);
-    if (rc != 1) return rc;
-  }
-  if (lay & CL_CF) return 2;   // only the persistent x6q writes [C][H][N][W]
-  if ((int64_t)Cin * H * W * 4 >= ((int64_t)1 << 31)) return 1;   // 32-bit buffer offsets
-  // the data gradient without forward statistics: 8-row tiles (channel-last,
-  // bf16 dy, the fused reduce)
-  const bool dg8 = dgrad && (!stats || fused);
-  if (y16 || (x16 && !(dg8 && b16))) return 2;   // bf16 storage: no such kernel
-  if (lay && !dg8) return 2;
-  if (dg8 && b16 && x16 && lay == (CL_X | CL_Y) && Cin == cdd::CI && Cout == cdd::COP && !bias &&
-      !sc && (!fused || bnr.y16) && dgrad16_dma()) {
+// The tiled kernels of a route (conv_x6_launch, at the end of this file,
+// switches here): CK_DGRAD_B16DMA, and CK_X6_TILED for the pairs where the
+// tiled kernel beats the exact f32 kernels on the model's shapes (r01_v9 op
+// timings): the encoder's 32->64 conv (1.17 vs 1.21 ms) and its 64->32 data
+// gradient (0.83 vs 0.98 ms).  r.dg8: 8-row tiles, two workgroups per CU.
+static int x6_tiled_launch(const ConvRoute& r, bool dgrad, const float* x, const float* w,
+                           const float* bias, const float* sc, const float* sh, float* y,
+                           double* stats, int64_t N, int Cin, int Cout, int64_t H, int64_t W,
+                           hipStream_t s, bool b16, bool x16, int lay, const Bnr& bnr) {
+  const dim3 grid((unsigned)r.gx, (unsigned)r.gy, (unsigned)r.gz);
+  if (r.kernel == CK_DGRAD_B16DMA) {
     const int ntr = (int)cdiv(H, cdd::TR), ntc = (int)cdiv(W, cdd::TC);
     const int64_t nt = N * (int64_t)ntr * ntc;
-    const int grid = (int)(nt < 256 ? nt : 256);   // one persistent workgroup per CU
-    *parts = grid;
-    // AINP_DGRAD16_WREG=0: weight fragments re-read from LDS per tile (A/B)
-    static const bool wreg = [] {
-      const char* e = getenv("AINP_DGRAD16_WREG");
-      return !(e && e[0] == '0');
-    }();
-    if (wreg)
-      hipLaunchKernelGGL(conv3x3_dgrad_b16dma_kernel<true>, dim3(grid), dim3(cdd::NT), 0, s,
-                         reinterpret_cast<const uint16_t*>(x), w, y, stats, bnr, (int)N, (int)H,
-                         (int)W, ntr, ntc, nt);
-    else
-      hipLaunchKernelGGL(conv3x3_dgrad_b16dma_kernel<false>, dim3(grid), dim3(cdd::NT), 0, s,
-                         reinterpret_cast<const uint16_t*>(x), w, y, stats, bnr, (int)N, (int)H,
-                         (int)W, ntr, ntc, nt);
+    hipLaunchKernelGGL(conv3x3_dgrad_b16dma_kernel<true>, grid, dim3(cdd::NT), 0, s,
+                       reinterpret_cast<const uint16_t*>(x), w, y, stats, bnr, (int)N, (int)H,
+                       (int)W, ntr, ntc, nt);
     return check_launch("conv3x3_dgrad_b16dma");
   }
-  *parts = dg8 ? N * cdiv(H, 8) * cdiv(W, cx6::TC) : N * cdiv(H, cx6::TR) * cdiv(W, cx6::TC);
-  const dim3 grid((unsigned)cdiv(W, cx6::TC), (unsigned)cdiv(H, cx6::TR), (unsigned)N);
   const int cop = Cout <= 32 ? 32 : 64;
 #define AINP_X6N(CIV, COV, NPV)                                                                \
   if (Cin == CIV && cop == COV) {                                                               \
-    if (dg8) {   /* 8-row tiles, two workgroups per CU */                                       \
-      const dim3 g8((unsigned)cdiv(W, cx6::TC), (unsigned)cdiv(H, 8), (unsigned)N);             \
+    if (r.dg8) {                                                                                \
       cl_dispatch(lay, [&](auto xl, auto yl) {                                                  \
         constexpr bool XL = decltype(xl)::value, YL = decltype(yl)::value;                      \
         if (NPV == 1 && x16)                                                                    \
-          hipLaunchKernelGGL((conv3x3_x6_kernel<CIV, COV, true, 1, NPV, true, XL, YL>), g8,     \
+          hipLaunchKernelGGL((conv3x3_x6_kernel<CIV, COV, true, 1, NPV, true, XL, YL>), grid,   \
                              dim3(cx6::NT), 0, s, x, w, bias, sc, sh, y, stats, Cout, (int)H,   \
                              (int)W, bnr);                                                      \
         else                                                                                    \
-          hipLaunchKernelGGL((conv3x3_x6_kernel<CIV, COV, true, 1, NPV, false, XL, YL>), g8,    \
+          hipLaunchKernelGGL((conv3x3_x6_kernel<CIV, COV, true, 1, NPV, false, XL, YL>), grid,  \
                              dim3(cx6::NT), 0, s, x, w, bias, sc, sh, y, stats, Cout, (int)H,   \
                              (int)W, bnr);                                                      \
       });                                                                                       \
@@ -1155,15 +1007,10 @@ int conv_x6_launch(bool dgrad, const float* x, const float* w, const float* bias
   } else {                                                                                    \
     AINP_X6N(CIV, COV, 3)                                                                     \
   }
-  // Only the pairs where this kernel beats the exact f32 kernels on the model's
-  // shapes (r01_v9 op timings): the encoder's 32->64 conv (1.17 vs 1.21 ms) and
-  // its 64->32 data gradient (0.83 vs 0.98 ms).  With 16 input channels (one K
-  // chunk) or a padded 16-channel output, the single resident workgroup per CU
-  // leaves the staging latency exposed and the exact kernels are faster.
   AINP_X6(32, 64) AINP_X6(64, 32)
 #undef AINP_X6
 #undef AINP_X6N
-  return 1;
+  return record_msg("conv3x3_x6: no tiled kernel for this pair");
 }
 
 // ------------------------------------------------------------------ wgrad
@@ -1478,8 +1325,7 @@ __global__ __launch_bounds__(CO / 32 * 3 * 64, 3) void conv3x3_wgrad_x6(
 //  * epilogue: the k-halves combined through LDS, one slab per workgroup in
 //    conv.hip's [CO][9*32 + 1] slab format (wgrad_reduce1 / wgrad_reduce).
 // The per-pixel work is HBM-bound (2*9*32*64 FLOP per 192 B of bf16 x + dy).
-namespace wdm {
-constexpr int TT = 24;                             // tile columns (3 row segments of 8)
+namespace wdm {   // (TT = 24 tile columns, 3 row segments of 8: conv_route.h)
 constexpr int HS = 32;                             // halo row stride (pixels)
 constexpr int NT = 512;                            // 8 waves
 constexpr int NW = NT / 64;
@@ -1518,13 +1364,11 @@ __device__ __forceinline__ void wdm_wait(int n) {
   }
 }
 
-// dbg (measurement only, AINP_WDM_DBG; wrong results): 1 = no MFMAs,
-// 2 = no prologue pass -- what the DMA ring / the pass alone cost
 template <int FT, int NS>
 __global__ __launch_bounds__(wdm::NT, 1) void conv3x3_wgrad_b16dma_kernel(
     const uint16_t* __restrict__ x, const float* __restrict__ in_scale,
     const float* __restrict__ in_shift, const uint16_t* __restrict__ dy,
-    float* __restrict__ partial, int N, int H, int W, int dbg) {
+    float* __restrict__ partial, int N, int H, int W) {
   using namespace wdm;
   using G = Geo<FT, NS>;
   constexpr int NPX = G::NPX, HC = G::HC, XPIX = G::XPIX, XBLK = G::XBLK, XB = G::XB;
@@ -1658,7 +1502,7 @@ __global__ __launch_bounds__(wdm::NT, 1) void conv3x3_wgrad_b16dma_kernel(
     else wdm_wait<QMAX - 1>(ahead);
     unsigned char* sx = smem + (i % NS) * STAGE;
     const unsigned char* sg = sx + XB;
-    if (pro && !(dbg & 2)) {
+    if (pro) {
       // act(x) in place, before the tile's barrier: each lane rewrites the 16
       // bytes its own DMA wrote (its vmcnt wait above retired them), so no
       // other wave's data is read here and the pass overlaps the other waves'
@@ -1700,7 +1544,6 @@ __global__ __launch_bounds__(wdm::NT, 1) void conv3x3_wgrad_b16dma_kernel(
     __builtin_amdgcn_s_barrier();   // tile i (DMAs + prologue) visible; stage i-1 free
     asm volatile("" ::: "memory");
     if (i + NS - 1 < cnt) issue(i + NS - 1);
-    if (dbg & 1) continue;
     // fragments of k-step ks+1 are read while the MFMAs of ks run (two
     // register sets); the bias slot's ones fragment is selected, not branched
     constexpr int KS = NPX / 32;
@@ -1775,15 +1618,6 @@ __global__ __launch_bounds__(wdm::NT, 1) void conv3x3_wgrad_b16dma_kernel(
       else if (li == 0) slab[co * (J + 1) + J] = v;    // the ones column: db
     }
   }
-}
-
-// AINP_WGRAD16_DMA=0: the register-staged kernel for that weight gradient (A/B)
-static bool wgrad16_dma() {
-  static const bool v = [] {
-    const char* e = getenv("AINP_WGRAD16_DMA");
-    return !(e && e[0] == '0');
-  }();
-  return v;
 }
 
 // Small-channel variant for (Cin pass, Cout) = (32, 16) and (16, 32): one of
@@ -2660,8 +2494,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x6q_kernel(
   }
 }
 
-// Persistent launcher (conv_x6_launch routes here); returns 1 if (CI, COP)
-// has no instantiation.  x16 / y16 (bf16 configuration, NP = 1 only): the
+// Persistent kernels: x16 / y16 (bf16 configuration, NP = 1 only): the
 // input (dy of a data gradient, act(x) source of a forward) / the forward
 // output in bf16 storage.  lay: CL_X (input channel-last) | CL_Y (output
 // channel-last).
@@ -2714,71 +2547,53 @@ static void x6q_go(dim3 g, hipStream_t s, bool b16, bool x16, bool y16, int lay,
   });
 }
 
-int conv_x6p_launch(bool dgrad, const float* x, const float* w, const float* bias,
-                    const float* sc, const float* sh, float* y, double* stats, int64_t N, int Cin,
-                    int Cout, int64_t H, int64_t W, hipStream_t s, int64_t* parts, bool b16,
-                    bool x16, bool y16, int lay, const Bnr& bnr) {
-  const int cop = Cout <= 32 ? 32 : 64;
-  if ((lay & CL_CF) && !(dgrad && Cin == 32 && Cout == 16 && !(lay & CL_Y)))
-    return 2;   // [C][H][N][W] dx: the 32 -> 16 data gradient (x6q) only
-  // bf16 channel-last forward with bf16 source and output: the LDS-DMA
-  // kernel, on x6p's grid (the same BatchNorm partial rows, bit-identical)
-  if (!dgrad && b16 && x16 && y16 && lay == (CL_X | CL_Y) && Cout % 4 == 0 && conv16_dma() &&
-      ((Cin == 32 && cop == 64) || (Cin == 16 && cop == 32))) {
-    const int g = (Cin == 32 ? 256 : 512) * conv_x6_occ16();
-    *parts = g;
-    const uint16_t* x16p = reinterpret_cast<const uint16_t*>(x);
-    uint16_t* y16p = reinterpret_cast<uint16_t*>(y);
-    // AINP_CONV16_RING=3: three halo buffers (exact-count buffer stores), A/B;
-    // default two (r06n / r06o: equal or faster, the DMA is not the limit)
-    static const int ring = [] {
-      const char* e = getenv("AINP_CONV16_RING");
-      return (e && e[0] == '3') ? 3 : 2;
-    }();
-    if (N * cdiv(H, cdf::TR) * cdiv(W, cdf::TC) >= ((int64_t)1 << 31))
-      return record_msg("conv3x3_fwd_b16dma: too many tiles");
-    const bool r3 = ring == 3 && N * H * W * Cout * 2 < ((int64_t)1 << 31) - 64;
-#define AINP_CF(CIV, COV, NTV, KR)                                                             \
-  do {                                                                                         \
-    if (r3)                                                                                    \
-      hipLaunchKernelGGL((conv3x3_fwd_b16dma_kernel<CIV, COV, NTV, 3, KR>), dim3(g), dim3(NTV), \
-                         0, s, x16p, w, bias, sc, sh, y16p, stats, (int)N, Cout, (int)H,        \
-                         (int)W);                                                               \
-    else                                                                                       \
-      hipLaunchKernelGGL((conv3x3_fwd_b16dma_kernel<CIV, COV, NTV, 2, KR>), dim3(g), dim3(NTV), \
-                         0, s, x16p, w, bias, sc, sh, y16p, stats, (int)N, Cout, (int)H,        \
-                         (int)W);                                                               \
-  } while (0)
-    if (Cin == 32) AINP_CF(32, 64, 1024, 0);
-    else AINP_CF(16, 32, 512, -1);
-#undef AINP_CF
-    return check_launch("conv3x3_fwd_b16dma");
+// The split-bf16 forward / data-gradient kernel the route chose; what stays
+// here is the template dispatch on the pair, the arithmetic, the storage and
+// the layouts.
+int conv_x6_launch(const ConvRoute& r, bool dgrad, const float* x, const float* w,
+                   const float* bias, const float* sc, const float* sh, float* y, double* stats,
+                   int64_t N, int Cin, int Cout, int64_t H, int64_t W, hipStream_t s, bool b16,
+                   bool x16, bool y16, int lay, const Bnr& bnr) {
+  const dim3 g((unsigned)r.gx);
+  switch (r.kernel) {
+    case CK_FWD_B16DMA: {
+      // two halo buffers (r06n / r06o: three were equal or slower, the DMA is
+      // not the limit)
+      const uint16_t* x16p = reinterpret_cast<const uint16_t*>(x);
+      uint16_t* y16p = reinterpret_cast<uint16_t*>(y);
+      if (Cin == 32)
+        hipLaunchKernelGGL((conv3x3_fwd_b16dma_kernel<32, 64, 1024, 2, 0>), g, dim3(1024), 0, s,
+                           x16p, w, bias, sc, sh, y16p, stats, (int)N, Cout, (int)H, (int)W);
+      else
+        hipLaunchKernelGGL((conv3x3_fwd_b16dma_kernel<16, 32, 512, 2, -1>), g, dim3(512), 0, s,
+                           x16p, w, bias, sc, sh, y16p, stats, (int)N, Cout, (int)H, (int)W);
+      return check_launch("conv3x3_fwd_b16dma");
+    }
+    case CK_X6P:
+      if (Cin == 32)
+        x6p_go<32, 64, false, 1024, 8>(g, s, b16, x16, y16, lay, x, w, bias, sc, sh, y, stats,
+                                       (int)N, Cout, (int)H, (int)W, bnr);
+      else if (dgrad)
+        x6p_go<16, 32, true, 512, 8>(g, s, b16, x16, y16, lay, x, w, bias, sc, sh, y, stats,
+                                     (int)N, Cout, (int)H, (int)W, bnr);
+      else
+        x6p_go<16, 32, false, 512, 8>(g, s, b16, x16, y16, lay, x, w, bias, sc, sh, y, stats,
+                                      (int)N, Cout, (int)H, (int)W, bnr);
+      return check_launch("conv3x3_x6p");
+    case CK_X6Q:
+      if (dgrad)
+        x6q_go<true>(g, s, b16, x16, y16, lay, x, w, bias, sc, sh, y, stats, (int)N, Cout, (int)H,
+                     (int)W, bnr);
+      else
+        x6q_go<false>(g, s, b16, x16, y16, lay, x, w, bias, sc, sh, y, stats, (int)N, Cout,
+                      (int)H, (int)W, bnr);
+      return check_launch("conv3x3_x6q");
+    default:
+      return x6_tiled_launch(r, dgrad, x, w, bias, sc, sh, y, stats, N, Cin, Cout, H, W, s, b16,
+                             x16, lay, bnr);
   }
-  // two workgroups per CU where the LDS allows it (one 16-channel chunk)
-#define AINP_X6P(CIV, COV, DG, G, NTV, TRV)                                                      \
-  if (dgrad == DG && Cin == CIV && cop == COV) {                                                 \
-    const int g2 = b16 ? (G) * conv_x6_occ16() : (G);                                            \
-    x6p_go<CIV, COV, DG, NTV, TRV>(dim3(g2), s, b16, x16, y16, lay, x, w, bias, sc, sh, y,      \
-                                   stats, (int)N, Cout, (int)H, (int)W, bnr);                    \
-    *parts = g2;                                                                                 \
-    return check_launch("conv3x3_x6p");                                                          \
-  }
-  AINP_X6P(32, 64, false, 256, 1024, 8)
-  AINP_X6P(16, 32, false, 512, 512, 8) AINP_X6P(16, 32, true, 512, 512, 8)
-  if (Cin == 32 && Cout == 16) {   // two workgroups per CU (65 KB of LDS; bf16: more)
-    const int gq = b16 ? 512 * conv_x6_occ16() : 512;
-    if (dgrad)
-      x6q_go<true>(dim3(gq), s, b16, x16, y16, lay, x, w, bias, sc, sh, y, stats, (int)N, Cout,
-                   (int)H, (int)W, bnr);
-    else
-      x6q_go<false>(dim3(gq), s, b16, x16, y16, lay, x, w, bias, sc, sh, y, stats, (int)N, Cout,
-                    (int)H, (int)W, bnr);
-    *parts = gq;
-    return check_launch("conv3x3_x6q");
-  }
-#undef AINP_X6P
-  return 1;
 }
+
 
 // conv3x3_wgrad_x6s tile rows, per plane count (AINP_X6S_FT1 for the bf16
 // configuration's NP = 1: 4, 8 or 16; AINP_X6S_FT3 for NP = 3: 4 or 8).
@@ -2796,20 +2611,21 @@ static int x6s_ft(int np) {
   return np == 1 ? rd("AINP_X6S_FT1", 4) : rd("AINP_X6S_FT3", 8);   // read per launch (tests)
 }
 
-// the split-bf16 weight-gradient kernels of one pass (NP planes, storage
-// G16 / XG16) for the (cp, Cout) pair; returns 1 if it has none
+// the split-bf16 weight-gradient kernel of one pass (WK_X6S / WK_X6; NP
+// planes, storage G16 / XG16) on r.gx persistent workgroups
 template <int NP, bool G16, bool XG16>
-static int wgrad_x6_go(const float* x, const float* sc, const float* sh, const float* dy,
-                       float* partial, int64_t N, int Cin, int Cout, int64_t H, int64_t W,
-                       int ci0, int cp, int grid, hipStream_t s, int lay) {
-  int rc = 1;
-  const int ft = x6s_ft(NP);
+static int wgrad_x6_go(const WgradRoute& r, const float* x, const float* sc, const float* sh,
+                       const float* dy, float* partial, int64_t N, int Cin, int64_t H, int64_t W,
+                       int ci0, hipStream_t s, int lay) {
+  int rc = AINP_OK;
+  const int ft = x6s_ft(NP), cp = r.cp;
+  const dim3 grid((unsigned)r.gx);
   auto go = [&](auto xlc, auto glc) {
     constexpr bool XL = decltype(xlc)::value, GL = decltype(glc)::value;
-    if ((cp == 32 && Cout == 16) || (cp == 16 && Cout == 32)) {
+    if (r.kernel == WK_X6S) {
 #define AINP_X6S(CPV, COV, FTV)                                                                  \
-  hipLaunchKernelGGL((conv3x3_wgrad_x6s<CPV, COV, NP, G16, XG16, XL, GL, FTV>), dim3(grid),     \
-                     dim3(384), 0, s, x, sc, sh, dy, partial, (int)N, Cin, (int)H, (int)W, ci0)
+  hipLaunchKernelGGL((conv3x3_wgrad_x6s<CPV, COV, NP, G16, XG16, XL, GL, FTV>), grid, dim3(384), \
+                     0, s, x, sc, sh, dy, partial, (int)N, Cin, (int)H, (int)W, ci0)
       if (cp == 32) {
         if (NP == 1 && ft == 16) AINP_X6S(32, 16, NP == 1 ? 16 : 8);
         else if (ft == 8) AINP_X6S(32, 16, 8);
@@ -2821,9 +2637,9 @@ static int wgrad_x6_go(const float* x, const float* sc, const float* sh, const f
       }
 #undef AINP_X6S
       rc = check_launch("conv3x3_wgrad_x6s");
-    } else if (cp == 32 && Cout == 64) {
-      hipLaunchKernelGGL((conv3x3_wgrad_x6<64, NP, G16, XG16, XL, GL>), dim3(grid), dim3(384), 0,
-                         s, x, sc, sh, dy, partial, (int)N, Cin, (int)H, (int)W, ci0);
+    } else {
+      hipLaunchKernelGGL((conv3x3_wgrad_x6<64, NP, G16, XG16, XL, GL>), grid, dim3(384), 0, s, x,
+                         sc, sh, dy, partial, (int)N, Cin, (int)H, (int)W, ci0);
       rc = check_launch("conv3x3_wgrad_x6");
     }
   };
@@ -2835,58 +2651,30 @@ static int wgrad_x6_go(const float* x, const float* sc, const float* sh, const f
   return rc;
 }
 
-// Launch the split-bf16 weight gradient of one 32-channel pass if Cout has an
-// instantiation; returns 1 if not handled.  grid = persistent workgroups.
-// g16 / x16 (bf16 configuration): dy / act(x)'s source in bf16 storage.
-// lay: CL_X (act(x) source channel-last) | CL_G (dy channel-last).
-int conv_wgrad_x6_launch(const float* x, const float* sc, const float* sh, const float* dy,
-                         float* partial, int64_t N, int Cin, int Cout, int64_t H, int64_t W,
-                         int ci0, int cp, int grid, hipStream_t s, bool b16, bool g16, bool x16,
-                         int lay, int* grid_used) {
-  *grid_used = grid;
-  // bf16 channel-last 32 -> 64 (the bf16 configuration's encoder conv): the
-  // LDS-DMA kernel, one workgroup per CU (its slabs: grid_used)
-  if (b16 && g16 && x16 && lay == (CL_X | CL_G) && Cin == 32 && cp == 32 && ci0 == 0 &&
-      Cout == 64 && wgrad16_dma()) {
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-      (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    const int g = ncu >= 16 ? ncu / 16 * 16 : 16;   // a multiple of WG_GROUPS (16)
-    if (N * ((H + 3) / 4) * ((W + wdm::TT - 1) / wdm::TT) >= ((int64_t)1 << 31))
-      return record_msg("conv3x3_wgrad_b16dma: too many tiles");
-    *grid_used = g;
-    static const int var = [] {
-      const char* e = getenv("AINP_WDM_VARIANT");
-      return e ? atoi(e) : 0;
-    }();
-    static const int dbg = [] {
-      const char* e = getenv("AINP_WDM_DBG");
-      return e ? atoi(e) : 0;
-    }();
-#define AINP_WDM(FTV, NSV)                                                                   \
-  hipLaunchKernelGGL((conv3x3_wgrad_b16dma_kernel<FTV, NSV>), dim3(g), dim3(wdm::NT), 0, s, \
-                     reinterpret_cast<const uint16_t*>(x), sc, sh,                          \
-                     reinterpret_cast<const uint16_t*>(dy), partial, (int)N, (int)H, (int)W, dbg)
-    // default: 8-row tiles, 2 stages (r06h sweep, standalone at the C3 shape:
-    // <8,2> 174 us, <4,4> 218, <4,5> 230, <4,6> 232; <8,3> needs more than
-    // 256 VGPRs with the fragment double buffer and spills)
-    switch (var) {
-      case 1: AINP_WDM(4, 5); break;
-      case 2: AINP_WDM(4, 6); break;
-      case 3: AINP_WDM(4, 4); break;
-      default: AINP_WDM(8, 2); break;
-    }
-#undef AINP_WDM
+// The split-bf16 weight gradient of one 32-channel pass on the kernel the
+// route chose (WK_X6S / WK_X6 / WK_B16DMA).  g16 / x16 (bf16 configuration):
+// dy / act(x)'s source in bf16 storage.  lay: CL_X (act(x) source
+// channel-last) | CL_G (dy channel-last).
+int conv_wgrad_x6_launch(const WgradRoute& r, const float* x, const float* sc, const float* sh,
+                         const float* dy, float* partial, int64_t N, int Cin, int Cout, int64_t H,
+                         int64_t W, int ci0, hipStream_t s, bool b16, bool g16, bool x16, int lay) {
+  (void)Cout;
+  if (r.kernel == WK_B16DMA) {
+    // 8-row tiles, 2 stages (r06h sweep, standalone at the C3 shape: <8,2>
+    // 174 us against 218-232 us for the 4-row rings; <8,3>
+    // needs more than 256 VGPRs with the fragment double buffer and spills)
+    hipLaunchKernelGGL((conv3x3_wgrad_b16dma_kernel<8, 2>), dim3((unsigned)r.gx), dim3(wdm::NT),
+                       0, s, reinterpret_cast<const uint16_t*>(x), sc, sh,
+                       reinterpret_cast<const uint16_t*>(dy), partial, (int)N, (int)H, (int)W);
     return check_launch("conv3x3_wgrad_b16dma");
   }
   if (b16) {
-    if (g16 && x16) return wgrad_x6_go<1, true, true>(x, sc, sh, dy, partial, N, Cin, Cout, H, W, ci0, cp, grid, s, lay);
-    if (g16) return wgrad_x6_go<1, true, false>(x, sc, sh, dy, partial, N, Cin, Cout, H, W, ci0, cp, grid, s, lay);
-    if (x16) return wgrad_x6_go<1, false, true>(x, sc, sh, dy, partial, N, Cin, Cout, H, W, ci0, cp, grid, s, lay);
-    return wgrad_x6_go<1, false, false>(x, sc, sh, dy, partial, N, Cin, Cout, H, W, ci0, cp, grid, s, lay);
+    if (g16 && x16) return wgrad_x6_go<1, true, true>(r, x, sc, sh, dy, partial, N, Cin, H, W, ci0, s, lay);
+    if (g16) return wgrad_x6_go<1, true, false>(r, x, sc, sh, dy, partial, N, Cin, H, W, ci0, s, lay);
+    if (x16) return wgrad_x6_go<1, false, true>(r, x, sc, sh, dy, partial, N, Cin, H, W, ci0, s, lay);
+    return wgrad_x6_go<1, false, false>(r, x, sc, sh, dy, partial, N, Cin, H, W, ci0, s, lay);
   }
-  return wgrad_x6_go<3, false, false>(x, sc, sh, dy, partial, N, Cin, Cout, H, W, ci0, cp, grid, s,
-                                      lay);
+  return wgrad_x6_go<3, false, false>(r, x, sc, sh, dy, partial, N, Cin, H, W, ci0, s, lay);
 }
 
 }  // namespace ainp

@@ -1175,7 +1175,7 @@ extern "C" int ainp_gemm_bf16nt(int64_t M, int64_t N, int64_t K, const uint16_t*
   if (M == 0 || N == 0) return AINP_OK;
   g16::Bias b{bias_a1, bias_a2, bias_b1, bias_b2, bias_nsplit};
   // large GEMMs on the 256 x 256 LDS-DMA kernel (bit-identical: same MFMA, same
-  // k order); ops._splitk_bf16 mirrors this rule for its split choice
+  // k order); ops._splitk_bf16 applies this rule to its split choice
   static const bool use256 = [] {  // AINP_GEMM16_256=0 keeps every GEMM on g16 (A/B runs)
     const char* e = getenv("AINP_GEMM16_256");
     return !(e && e[0] == '0');

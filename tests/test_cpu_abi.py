@@ -122,6 +122,13 @@ def test_dy16_routing_query():
     assert rc == -1 and b"YCFNT" in _lib.lib.ainp_last_error()
     rc = _lib.lib.ainp_conv3x3_dgrad_ex(1, 1, 1, None, 1, 16, 32, 8, 8, 256 | 64, None)
     assert rc == -1 and b"bad argument" in _lib.lib.ainp_last_error()
+    # the partials-only data gradient (dx == NULL): Conv2d(16, 1) with fp32 dy,
+    # channel-last dx (64 = AINP_CONV_YCL) only
+    q = _lib.lib.ainp_conv3x3_dgrad_bnr_nodx_ok
+    assert q(32, 16, 1, 257, 334, 64, 0) == 1 and q(32, 16, 1, 257, 334, 64 | 32, 2) == 1
+    assert q(32, 16, 1, 257, 334, 0, 0) == 0 and q(32, 16, 1, 257, 334, 64 | 2 | 4, 0) == 0
+    for cin, cout in ((16, 2), (16, 32), (32, 16), (1, 16)):
+        assert q(32, cin, cout, 257, 334, 64, 0) == 0, (cin, cout)
     # the fused first-conv weight gradient + BatchNorm apply: Conv2d(1, 16) only
     rc = _lib.lib.ainp_conv3x3_wgrad_bnapply(16, None, None, 16, 16, 16, 16, None, 16, 16, 8, 16,
                                              16, 16, 16, 16, 1, 16, 32, 8, 8, None)
@@ -142,7 +149,8 @@ HOST_ONLY = {"ainp_abi_version", "ainp_build_target", "ainp_last_error", "ainp_r
              "ainp_flac_info", "ainp_flac_decode", "ainp_flac_encode_bound", "ainp_flac_encode",
              "ainp_l1_pow10_loss_slots", "ainp_range_push", "ainp_range_pop", "ainp_mark",
              "ainp_conv16_set_variant", "ainp_conv3x3_dy16_ok", "ainp_conv3x3_io16_ok",
-             "ainp_conv3x3_cl_ok", "ainp_conv3x3_dgrad_cfnt_ok"}
+             "ainp_conv3x3_cl_ok", "ainp_conv3x3_dgrad_cfnt_ok",
+             "ainp_conv3x3_dgrad_bnr_nodx_ok"}
 
 
 def test_torch_library_registers_every_gpu_entry_point():

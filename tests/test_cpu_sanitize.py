@@ -9,7 +9,11 @@ the host C++ that parses untrusted input runs under ASan + UBSan on the CPU:
   stereo, ragged last blocks) -- tests/sanitize/flac_fuzz.cpp.
 
 The torch.ops.ainp host layer (csrc/torch_ops.cpp) is built with UBSan as
-libainp_torch_ubsan.so; test_gpu_sanitize.py runs it on the GPU box."""
+libainp_torch_ubsan.so; test_gpu_sanitize.py runs it on the GPU box.
+
+  csrc/conv_route.h (which 3x3 conv kernel serves which call, and every
+  host-only query derived from it): tests/sanitize/conv_route_check.cpp walks
+  the routing table, the accepted extremes included, as a stand-alone program."""
 import glob
 import os
 import subprocess
@@ -48,3 +52,42 @@ def test_torch_ops_ubsan_library_built(sanitize_build):
     assert os.path.exists(so)
     r = subprocess.run(["readelf", "-d", so], capture_output=True, text=True)
     assert "libubsan" in r.stdout
+
+
+def test_conv_route_table_under_asan_ubsan(sanitize_build):
+    """Every cell of the routing table refuses with a known message or names a
+    kernel whose grid / row counts fit what the launchers cast them to and the
+    workspace bounds, with no overflow at N = 65535, H = W = 2^24 (2^31 - 1
+    for the data gradient); and the model's convs run the kernels DESIGN
+    section 4 names."""
+    exe = os.path.join(os.path.dirname(sanitize_build), "conv_route_check")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    env.pop("LD_PRELOAD", None)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-3000:]
+    assert "conv_route_check OK" in out
+    assert "runtime error" not in out and "AddressSanitizer" not in out, out[-3000:]
+    # "model <fp32|bf16> <Cin>-><Cout> fwd=<kernel> dgrad=<kernel> wgrad=<kernel>"
+    model = {tuple(line.split()[1:3]): dict(kv.split("=") for kv in line.split()[3:])
+             for line in out.splitlines() if line.startswith("model ")}
+    assert len(model) == 10
+    for prec in ("fp32", "bf16"):
+        # row strips for 1 <-> 16 (the data gradient of the 16 -> 1 conv runs 1 -> 16)
+        assert model[prec, "1->16"]["fwd"] == "rows_1to16"
+        assert model[prec, "16->1"]["fwd"] == "rows_16to1"
+        assert model[prec, "16->1"]["dgrad"] == "rows_1to16"
+        assert model[prec, "1->16"]["wgrad"] == model[prec, "16->1"]["wgrad"] == "strip_cl"
+        # x6q for 32 -> 16, forward and the 16 -> 32 conv's data gradient
+        assert model[prec, "32->16"]["fwd"] == "x6q" and model[prec, "16->32"]["dgrad"] == "x6q"
+        assert model[prec, "32->16"]["dgrad"] == "x6p"
+    # x6p for 16 -> 32 and 32 -> 64
+    assert model["fp32", "16->32"]["fwd"] == model["fp32", "32->64"]["fwd"] == "x6p"
+    assert model["fp32", "32->64"]["dgrad"] == "x6_tiled"
+    assert [model["fp32", p]["wgrad"] for p in ("16->32", "32->64", "32->16")] == \
+        ["x6s", "x6", "x6s"]
+    # the LDS-DMA kernels under bf16 with bf16 channel-last source and output
+    assert model["bf16", "16->32"]["fwd"] == model["bf16", "32->64"]["fwd"] == "fwd_b16dma"
+    assert model["bf16", "32->64"]["dgrad"] == "dgrad_b16dma"
+    assert model["bf16", "32->64"]["wgrad"] == "wgrad_b16dma"

@@ -74,6 +74,35 @@ def test_cl_fwd_bit_identical(cin, cout, N, H, W, bf16):
 
 
 @pytest.mark.parametrize("bf16", [False, True])
+@pytest.mark.parametrize("N,H,W", [(1, 1, 1), (2, 9, 49)])
+@pytest.mark.parametrize("cin,cout", [(1, 16), (16, 32), (32, 64), (32, 16), (16, 1)])
+def test_fwd_stat_rows_query_matches_launch(cin, cout, N, H, W, bf16):
+    """ainp_conv3x3_fwd_stat_rows_ex and the forward are one routing decision
+    (csrc/conv_route.h): a statistics buffer of exactly the queried rows,
+    filled with NaN, is fully defined by the launch (rows the kernel does not
+    write are zeroed), and its fixed-order sum is the sum / sum of squares of
+    the y the launch wrote -- at the tolerance of the neighbouring statistics
+    tests (1e-6 fp32 above, 2e-5 for the bf16 arithmetic in test_gpu_kernels),
+    NCHW and in the model's channel-last layout."""
+    from ainp import ops
+    x, dy, w, b, sc, sh = _data(N, cin, cout, H, W, cin * 100 + cout + N)
+    flags = ops.CONV_BF16 if bf16 else 0
+    rows = ops._lib.lib.ainp_conv3x3_fwd_stat_rows_ex(N, cin, cout, H, W, flags)
+    assert rows >= 1
+    for cl in (False, True):
+        stats = torch.full((rows, 2 * cout), float("nan"), device=DEV, dtype=torch.float64)
+        y = torch.empty((N, H, W, cout) if cl else (N, cout, H, W), device=DEV)
+        torch.ops.ainp.conv3x3_fwd(_cl(x) if cl else x, w, b, sc, sh, y, stats,
+                                   flags | ((ops.CONV_XCL | ops.CONV_YCL) if cl else 0))
+        assert not torch.isnan(stats).any(), cl
+        sums = ops.bn_stats_reduce(stats, cout)
+        yd = (_nchw(y) if cl else y).double()
+        tol = 2e-5 if bf16 else 1e-6
+        assert rel(sums[:cout], yd.sum((0, 2, 3))) < tol, cl
+        assert rel(sums[cout:], (yd * yd).sum((0, 2, 3))) < tol, cl
+
+
+@pytest.mark.parametrize("bf16", [False, True])
 @pytest.mark.parametrize("N,H,W", SHAPES)
 @pytest.mark.parametrize("cin,cout", PAIRS)
 def test_cl_dgrad_wgrad_bit_identical(cin, cout, N, H, W, bf16):
