@@ -124,6 +124,41 @@ int ainp_gl_stft_update(const float* audio, int64_t n_signals, int64_t n_samples
 int ainp_gl_update(const float* rebuilt, float* tprev, float* angles, int64_t n,
                    float momentum, int first, void* stream);
 
+/* Mel projection, utils.extract_mel_spectrogram -> librosa.feature.melspectrogram
+ * (utils.py:268): out[s][m][t] = sum_f w[m][f] * |spec[s][f][t]|^power, the power
+ * spectrogram formed on the fly (never stored).  spec: the complex STFT
+ * [n_signals][n_bins][n_frames] as complex64 (dtype 0, out float32) or
+ * complex128 (dtype 1, out float64), as ainp_stft writes it; out
+ * [n_signals][n_mels][n_frames], accumulated in the output type as one fma
+ * chain over ascending bins (deterministic, no atomics).  power 2 -> re^2+im^2,
+ * 1 -> one sqrt, else pow; finite and >= 0.
+ * The filterbank w (librosa.filters.mel: Slaney scale and normalisation,
+ * float32) is passed banded: row m is non-zero on bins band_lo[m] ..
+ * band_lo[m] + len - 1 with len = band_off[m+1] - band_off[m] (0: an empty
+ * band, its output row is 0), its values at weights[band_off[m] ..
+ * band_off[m+1]); band_lo int32 [n_mels], band_off int32 [n_mels + 1],
+ * weights float32 [n_weights], all device.  The caller checks the tables on the
+ * host (ainp/mel.py); a band whose run leaves [0, n_bins) or the weights is
+ * skipped by the kernel. */
+int ainp_mel_fwd(const void* spec, int dtype, int64_t n_signals, int n_bins,
+                 int64_t n_frames, const int32_t* band_lo, const int32_t* band_off,
+                 const float* weights, int64_t n_weights, int n_mels, double power,
+                 void* out, void* stream);
+
+/* Mel -> linear spectrogram, utils.mel_spectrogram_to_audio (utils.py:379-383):
+ * out[s][f][t] = epilogue(sum_k pinv[f][k] * mel[s][k][t]); pinv float32
+ * [n_bins][n_mels] (np.linalg.pinv of the filterbank, host-computed), mel
+ * float32 [n_signals][n_mels][n_frames], out float32 [n_signals][n_bins][n_frames].
+ * Exact f32 fma chain on the f32 MFMA (fixed k order, deterministic); the sum
+ * is the same bits whichever epilogue follows it.  flags: 0 the bare product
+ * (the reference's power != 2 path); AINP_MEL_SQRT sqrt(x) -- NaN where the
+ * product is negative, as numpy; AINP_MEL_SQRT | AINP_MEL_CLAMP sqrt(max(x, 0));
+ * AINP_MEL_CLAMP alone max(x, 0). */
+#define AINP_MEL_SQRT 1
+#define AINP_MEL_CLAMP 2
+int ainp_mel_inverse(const float* pinv, const float* mel, int64_t n_signals, int n_bins,
+                     int n_mels, int64_t n_frames, int flags, float* out, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* fp32 GEMM on MFMA (fp32-accurate bf16 split by default, exact f32 on flag) */
 /* ------------------------------------------------------------------------ */

@@ -225,6 +225,10 @@ _SIGS = {
     "ainp_gram_sign_sym": (c_int, [P, P, c_int64, c_int, P, c_float, P, P]),
     "ainp_gan_recon_bwd": (c_int, [P, P, P, c_int64, P, P, c_double, P, P]),
     "ainp_conv_weight_flip_t": (c_int, [P, c_int, c_int, c_int, P, P]),
+    # mel projection and its pseudo-inverse (csrc/mel.hip)
+    "ainp_mel_fwd": (c_int, [P, c_int, c_int64, c_int, c_int64, P, P, P, c_int64, c_int,
+                             c_double, P, P]),
+    "ainp_mel_inverse": (c_int, [P, P, c_int64, c_int, c_int, c_int64, c_int, P, P]),
 }
 
 EXPORTED = tuple(_SIGS)

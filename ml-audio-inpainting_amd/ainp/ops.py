@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import mel as _mel
 
 # AINP_TORCH_OPS: another build of the same registration (e.g. the UBSan build
 # libainp_torch_ubsan.so that tests/test_gpu_sanitize.py loads)
@@ -47,7 +48,8 @@ def _release_device_caches():
             torch.cuda.synchronize()
     except Exception:   # noqa: BLE001 -- best effort at interpreter exit
         pass
-    for c in (_WIN_CACHE, _GEMM_WS, _EMPTY, _WT_CACHE, _WT16_CACHE, _RED_WS):
+    for c in (_WIN_CACHE, _GEMM_WS, _EMPTY, _WT_CACHE, _WT16_CACHE, _RED_WS,
+              _mel._DEVICE_CACHE):
         c.clear()
 
 
@@ -2048,3 +2050,85 @@ def griffinlim(S, n_iter=32, hop_length=None, win_length=None, n_fft=None, windo
             _T.gl_update(rebuilt, tprev, angles, float(momentum), it == 0)
     return istft(mag=S, angles=angles, n_fft=n_fft, hop_length=hop_length,
                  win_length=win_length, window=window, center=center)
+
+
+# ==================================================================== mel
+MEL_SQRT = 1           # include/ainp.h AINP_MEL_SQRT
+MEL_CLAMP = 2          # AINP_MEL_CLAMP
+
+
+def mel_fwd(spec, bands, power=2.0):
+    """ainp_mel_fwd: spec [n_signals, F, T] complex64 / complex128 cuda ->
+    [n_signals, n_mels, T] float32 / float64, out[m] = sum_f w[m, f] |spec[f]|^power.
+    bands: the filterbank as band tables on spec's device (ainp.mel.device_bands;
+    checked against its bin count on the host when they are built)."""
+    _req(spec, "spec", dtype=None)
+    if spec.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("spec must be complex64 or complex128")
+    if spec.dim() != 3:
+        raise ValueError("spec must be [n_signals, n_bins, n_frames]")
+    if spec.shape[1] != bands.n_bins:
+        raise ValueError(f"spec has {spec.shape[1]} bins, the mel bands were built for "
+                         f"{bands.n_bins}")
+    if not (power >= 0 and math.isfinite(power)):
+        raise ValueError("power must be finite and non-negative")
+    rdt = torch.float32 if spec.dtype == torch.complex64 else torch.float64
+    out = torch.empty(spec.shape[0], bands.lo.numel(), spec.shape[2], device=spec.device,
+                      dtype=rdt)
+    _T.mel_fwd(spec, bands.lo, bands.off, bands.weights, float(power), out)
+    return out
+
+
+def mel_spectrogram(audio=None, *, S=None, sr=22050, n_fft=2048, hop_length=512,
+                    win_length=None, window="hann", center=True, n_mels=128, fmin=0.0,
+                    fmax=None, power=2.0):
+    """librosa.feature.melspectrogram on the GPU: audio [..., S] float32 /
+    float64 cuda -> [..., n_mels, T] of the same precision (ops.stft, then
+    ainp_mel_fwd: the power spectrogram is formed inside the projection and
+    never stored).  S: the complex STFT [..., n_fft/2+1, T] instead of audio."""
+    if (audio is None) == (S is None):
+        raise ValueError("give either audio or S (the complex STFT)")
+    if S is None:
+        S = stft(audio, n_fft, hop_length, win_length, window, center)
+    else:
+        _req(S, "S", dtype=None)
+    lead, (F, T) = S.shape[:-2], S.shape[-2:]
+    if F != n_fft // 2 + 1:
+        raise ValueError(f"S has {F} bins, n_fft={n_fft} gives {n_fft // 2 + 1}")
+    bands = _mel.device_bands(sr, n_fft, n_mels, fmin, fmax, S.device)
+    out = mel_fwd(S.reshape(-1, F, T).contiguous(), bands, power)
+    return out.reshape(*lead, n_mels, T)
+
+
+def mel_inverse(pinv, mel, flags=0):
+    """ainp_mel_inverse: pinv [F, n_mels] @ mel [n_signals, n_mels, T] (float32
+    cuda) -> [n_signals, F, T], with the MEL_SQRT / MEL_CLAMP epilogue."""
+    _req(pinv, "pinv")
+    _req(mel, "mel")
+    if pinv.dim() != 2 or mel.dim() != 3 or mel.shape[1] != pinv.shape[1]:
+        raise ValueError("mel_inverse wants pinv [F, n_mels] and mel [n_signals, n_mels, T]")
+    if flags & ~(MEL_SQRT | MEL_CLAMP):
+        raise ValueError("unknown mel_inverse flags")
+    out = torch.empty(mel.shape[0], pinv.shape[0], mel.shape[2], device=mel.device,
+                      dtype=torch.float32)
+    _T.mel_inverse(pinv, mel, int(flags), out)
+    return out
+
+
+def mel_to_linear(M, sr=22050, n_fft=2048, n_mels=128, fmin=0.0, fmax=None, power=2.0,
+                  clamp_negative=True):
+    """The reference's mel -> linear step (utils.py:367-383): pinv(mel basis) @ M,
+    and its square root when power == 2.0 exactly.  M [..., n_mels, T] float32
+    cuda -> [..., n_fft/2+1, T].  The product has negative entries; the
+    reference's sqrt turns them into NaN, clamp_negative zeroes them first
+    (reference quirks); it has no effect when power != 2.0."""
+    _req(M, "M")
+    lead, (K, T) = M.shape[:-2], M.shape[-2:]
+    if K != n_mels:
+        raise ValueError(f"M has {K} mel bands, n_mels={n_mels}")
+    P = _mel.device_pinv(sr, n_fft, n_mels, fmin, fmax, M.device)
+    flags = 0
+    if power == 2.0:
+        flags = MEL_SQRT | (MEL_CLAMP if clamp_negative else 0)
+    out = mel_inverse(P, M.reshape(-1, K, T).contiguous(), flags)
+    return out.reshape(*lead, P.shape[0], T)

@@ -165,6 +165,50 @@ void gl_update(const Tensor& rebuilt, const Tensor& tprev, const Tensor& angles,
       "gl_update");
 }
 
+// -------------------------------------------------------------------- mel
+void mel_fwd(const Tensor& spec, const Tensor& band_lo, const Tensor& band_off,
+             const Tensor& weights, double power, const Tensor& out) {
+  GUARD(spec);
+  TORCH_CHECK(spec.dim() == 3, "spec must be [n_signals, n_bins, n_frames]");
+  TORCH_CHECK(out.dim() == 3, "out must be [n_signals, n_mels, n_frames]");
+  const bool f64 = spec.scalar_type() == at::kComplexDouble;
+  const void* x = dev<void>(spec, "spec", f64 ? at::kComplexDouble : at::kComplexFloat);
+  void* o = dev<void>(out, "out", f64 ? at::kDouble : at::kFloat);
+  const int64_t n_mels = out.size(1);
+  TORCH_CHECK(out.size(0) == spec.size(0) && out.size(2) == spec.size(2), "out is ",
+              out.sizes(), ", expected [", spec.size(0), ", n_mels, ", spec.size(2), "]");
+  same_device(spec, out);
+  same_device(spec, band_lo);
+  same_device(spec, band_off);
+  same_device(spec, weights);
+  numel_is(band_lo, n_mels, "band_lo");
+  numel_is(band_off, n_mels + 1, "band_off");
+  chk(ainp_mel_fwd(x, f64 ? 1 : 0, spec.size(0), (int)spec.size(1), spec.size(2),
+                   dev<int32_t>(band_lo, "band_lo", at::kInt),
+                   dev<int32_t>(band_off, "band_off", at::kInt), dev(weights, "weights"),
+                   weights.numel(), (int)n_mels, power, o, stream_of(spec)),
+      "mel_fwd");
+}
+
+void mel_inverse(const Tensor& pinv, const Tensor& mel, int64_t flags, const Tensor& out) {
+  GUARD(mel);
+  TORCH_CHECK(pinv.dim() == 2, "pinv must be [n_bins, n_mels]");
+  TORCH_CHECK(mel.dim() == 3, "mel must be [n_signals, n_mels, n_frames]");
+  TORCH_CHECK(out.dim() == 3, "out must be [n_signals, n_bins, n_frames]");
+  TORCH_CHECK(mel.size(1) == pinv.size(1), "mel has ", mel.size(1), " bands, pinv ",
+              pinv.size(1));
+  TORCH_CHECK(out.size(0) == mel.size(0) && out.size(1) == pinv.size(0) &&
+                  out.size(2) == mel.size(2),
+              "out is ", out.sizes(), ", expected [", mel.size(0), ", ", pinv.size(0), ", ",
+              mel.size(2), "]");
+  same_device(mel, pinv);
+  same_device(mel, out);
+  chk(ainp_mel_inverse(dev(pinv, "pinv"), dev(mel, "mel"), mel.size(0), (int)pinv.size(0),
+                       (int)pinv.size(1), mel.size(2), (int)flags, dev(out, "out"),
+                       stream_of(mel)),
+      "mel_inverse");
+}
+
 // ------------------------------------------------------------------- GEMM
 void gemm(int64_t M, int64_t N, int64_t K, double alpha, at::TensorList A, int64_t sam,
           int64_t sak, int64_t strideA, at::TensorList B, int64_t sbk, int64_t sbn,
@@ -1785,6 +1829,9 @@ TORCH_LIBRARY(ainp, m) {
   m.def("gan_recon_bwd(Tensor g, Tensor o, Tensor m, Tensor sums5, Tensor gout3, float n_total, "
         "Tensor(a!) out) -> ()");
   m.def("conv_weight_flip_t(Tensor w, Tensor(a!) out) -> ()");
+  m.def("mel_fwd(Tensor spec, Tensor band_lo, Tensor band_off, Tensor weights, float power, "
+        "Tensor(a!) out) -> ()");
+  m.def("mel_inverse(Tensor pinv, Tensor mel, int flags, Tensor(a!) out) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
@@ -1869,6 +1916,8 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("gram_sign_sym", &gram_sign_sym);
   m.impl("gan_recon_bwd", &gan_recon_bwd);
   m.impl("conv_weight_flip_t", &conv_weight_flip_t);
+  m.impl("mel_fwd", &mel_fwd);
+  m.impl("mel_inverse", &mel_inverse);
 }
 
 // The ops write through raw device pointers like the C ABI; autograd is the
@@ -1956,4 +2005,6 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("gram_sign_sym", torch::CppFunction::makeFallthrough());
   m.impl("gan_recon_bwd", torch::CppFunction::makeFallthrough());
   m.impl("conv_weight_flip_t", torch::CppFunction::makeFallthrough());
+  m.impl("mel_fwd", torch::CppFunction::makeFallthrough());
+  m.impl("mel_inverse", torch::CppFunction::makeFallthrough());
 }

@@ -1,4 +1,4 @@
-"""Drop-in for the reference's utils.py (audio I/O, gap creation, STFT).
+"""Drop-in for the reference's utils.py (audio I/O, gap creation, STFT, mel).
 
 Same names, signatures, return types and error behaviour as
 /root/reference/utils.py; the STFT runs on the MI355X kernel
@@ -13,7 +13,12 @@ Same names, signatures, return types and error behaviour as
   extract_spectrogram   utils.py:192-234 (GPU, returns the complex STFT; power is
                                           validated then ignored)
   spectrogram_to_audio  utils.py:279-333  (GPU ISTFT / Griffin-Lim)
-Mel spectrograms and plotting are outside the hot path.
+  extract_mel_spectrogram   utils.py:236-277 (GPU: ainp_stft + ainp_mel_fwd, the
+                                          Slaney filterbank of ainp/mel.py)
+  mel_spectrogram_to_audio  utils.py:335-393 (GPU: ainp_mel_inverse + Griffin-Lim;
+                                          clamp_negative deviates from the
+                                          reference's NaN, see its docstring)
+Plotting (visualize_spectrogram) is outside the hot path.
 """
 from __future__ import annotations
 
@@ -258,12 +263,64 @@ def spectrogram_to_audio(spectrogram, phase=None, phase_info: bool = False, n_ff
     return y.cpu().numpy() if as_numpy else y
 
 
-def extract_mel_spectrogram(*args, **kwargs):
-    raise NotImplementedError("mel spectrograms are outside the hot path (DESIGN.md §1)")
+def extract_mel_spectrogram(audio_data, sample_rate: int = DEFAULT_SAMPLE_RATE,
+                            n_fft: int = 2048, hop_length: int = 512, n_mels: int = 128,
+                            fmin: float = 0.0, fmax: Optional[float] = None,
+                            power: float = 2.0):
+    """utils.py:236-277 -> librosa.feature.melspectrogram on the GPU: the STFT
+    (win_length = n_fft, hann, center=True, zero padding) by ainp_stft, then
+    mel_basis @ |X|**power by ainp_mel_fwd with the Slaney filterbank of
+    librosa.filters.mel (ainp/mel.py); the power spectrogram is never stored.
+    float32 in -> float32 out, float64 -> float64 (as librosa).  numpy in ->
+    numpy out; a torch cuda tensor stays on the GPU."""
+    if power < 0:
+        raise ValueError("Power must be non-negative")
+    import torch
+    from ainp import ops
+    kw = dict(sr=sample_rate, n_fft=n_fft, hop_length=hop_length, n_mels=n_mels, fmin=fmin,
+              fmax=fmax, power=power)
+    if isinstance(audio_data, torch.Tensor):
+        return ops.mel_spectrogram(audio_data, **kw)
+    a = np.asarray(audio_data)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float32 if a.dtype.itemsize <= 4 else np.float64)
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return ops.mel_spectrogram(t, **kw).cpu().numpy()
 
 
-def mel_spectrogram_to_audio(*args, **kwargs):
-    raise NotImplementedError("mel spectrograms are outside the hot path (DESIGN.md §1)")
+def mel_spectrogram_to_audio(mel_spectrogram, sample_rate: int = DEFAULT_SAMPLE_RATE,
+                             n_fft: int = 2048, hop_length: int = 512, n_iter: int = 32,
+                             n_mels: int = 128, fmin: float = 0.0,
+                             fmax: Optional[float] = None, power: float = 2.0, *,
+                             clamp_negative: bool = True, random_state=None):
+    """utils.py:335-393 on the GPU: linear = pinv(mel_basis) @ mel (pinv on the
+    host, as the reference; the product by ainp_mel_inverse), its square root
+    when power == 2.0 exactly, then Griffin-Lim (n_iter, librosa's defaults:
+    win_length = n_fft, hann, center, momentum 0.99, random initial phases;
+    random_state seeds them as in librosa).  Returns hop_length * (T - 1)
+    samples, float32.  numpy in -> numpy out; a torch cuda tensor stays on the GPU.
+
+    Deviation (clamp_negative, keyword-only, not in the reference): the
+    pseudo-inverse product is slightly negative in a few bins (measured: 0.3 % of
+    the entries and 97 % of the frames at 16 kHz / n_fft 2048 / 128 mels; 3 % and
+    100 % at n_fft 128 / 20 mels), the reference's np.sqrt turns those into NaN
+    and the overlap-add spreads them over the whole signal, which its own tests
+    (len > 0, not allclose(0)) do not notice.  clamp_negative=True (default)
+    zeroes negative values before the sqrt; clamp_negative=False reproduces the
+    reference's NaN.  With power != 2.0 no sqrt is taken and the negative
+    magnitudes go to Griffin-Lim as they are, as in the reference."""
+    import torch
+    from ainp import ops
+    as_numpy = not isinstance(mel_spectrogram, torch.Tensor)
+    M = mel_spectrogram
+    if as_numpy:
+        M = torch.from_numpy(np.ascontiguousarray(np.asarray(M))).cuda()
+    M = M.to(torch.float32).contiguous()
+    linear = ops.mel_to_linear(M, sr=sample_rate, n_fft=n_fft, n_mels=n_mels, fmin=fmin,
+                               fmax=fmax, power=power, clamp_negative=clamp_negative)
+    y = ops.griffinlim(linear, n_iter=n_iter, hop_length=hop_length, n_fft=n_fft,
+                       random_state=random_state)
+    return y.cpu().numpy() if as_numpy else y
 
 
 def visualize_spectrogram(*args, **kwargs):
