@@ -159,6 +159,42 @@ int ainp_mel_fwd(const void* spec, int dtype, int64_t n_signals, int n_bins,
 int ainp_mel_inverse(const float* pinv, const float* mel, int64_t n_signals, int n_bins,
                      int n_mels, int64_t n_frames, int flags, float* out, void* stream);
 
+/* Gap-wise Janssen autoregressive inpainting, the AR row of the reference's
+ * model comparison (models/AudioReg/utils/janssen_inp.m, method "lpc", as
+ * models/AudioReg/train.m drives it).  Float64 throughout.  sol
+ * [n_segments][stride] holds one segment per row, updated in place: segment i
+ * is sol[i][0 .. n[i]) with the single run of missing samples
+ * [gap_start[i], gap_start[i] + gap_len[i]); whatever the gap holds on entry
+ * is replaced by zeros first, the observed samples are never written.  Each of
+ * maxit iterations: biased autocorrelation r[0..p] of the current solution,
+ * Levinson-Durbin to the AR coefficients a, b = autocorrelation of a, then the
+ * gap samples z from sum_{j in gap} b[|i-j|] z_j = -sum_{j observed, |i-j| <= p}
+ * b[|i-j|] x_j (symmetric positive-definite Toeplitz; Levinson recursion).
+ * One workgroup per segment for all iterations, fixed-order reductions, no
+ * atomics: the same bits on every call.
+ * iters_done int32 [n_segments]: iterations completed -- 0 for a silent
+ * context (r[0] == 0, the gap stays zero); fewer than maxit when a pivot of
+ * the Toeplitz solve was non-positive or a value non-finite (the previous
+ * iterate stays, the reference's chol break); -1 for a segment whose table
+ * entries are outside the supported range (left untouched).
+ * history (nullable) [n_segments][maxit][max_i gap_len[i]]: the gap after each
+ * completed iteration (the reference's saveall); other entries are not written.
+ * The kernel takes the row length from the table itself, with every entry
+ * clamped to [0, 2048]: an out-of-range gap_len (its segment is skipped) counts
+ * as clamped, so size history from valid tables only.
+ * n, gap_start, gap_len: int32 [n_segments], device; the caller checks them on
+ * the host (ainp/janssen.py) and the kernel guards them.
+ * Supported: 1 <= p <= 3072, p < n[i] <= min(stride, 16384), 1 <= gap_len[i]
+ * <= 2048 inside the segment, 1 <= maxit <= 1000.  workspace: at least
+ * ainp_janssen_workspace(n_segments, max n, p, max gap_len) bytes (device;
+ * may be NULL when that is 0 -- today every vector of the recursions fits LDS
+ * over the whole supported range and the query returns 0). */
+int ainp_janssen(double* sol, int64_t n_segments, int64_t stride, const int32_t* n,
+                 const int32_t* gap_start, const int32_t* gap_len, int p, int maxit,
+                 double* history, int32_t* iters_done, void* workspace, size_t workspace_bytes,
+                 void* stream);
+size_t ainp_janssen_workspace(int64_t n_segments, int n_max, int p, int gap_max);
+
 /* ------------------------------------------------------------------------ */
 /* fp32 GEMM on MFMA (fp32-accurate bf16 split by default, exact f32 on flag) */
 /* ------------------------------------------------------------------------ */

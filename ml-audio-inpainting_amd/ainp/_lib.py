@@ -229,6 +229,9 @@ _SIGS = {
     "ainp_mel_fwd": (c_int, [P, c_int, c_int64, c_int, c_int64, P, P, P, c_int64, c_int,
                              c_double, P, P]),
     "ainp_mel_inverse": (c_int, [P, P, c_int64, c_int, c_int, c_int64, c_int, P, P]),
+    # Janssen autoregressive gap inpainting (csrc/janssen.hip)
+    "ainp_janssen": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
+    "ainp_janssen_workspace": (c_size_t, [c_int64, c_int, c_int, c_int]),
 }
 
 EXPORTED = tuple(_SIGS)

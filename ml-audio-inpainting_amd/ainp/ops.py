@@ -2132,3 +2132,41 @@ def mel_to_linear(M, sr=22050, n_fft=2048, n_mels=128, fmin=0.0, fmax=None, powe
         flags = MEL_SQRT | (MEL_CLAMP if clamp_negative else 0)
     out = mel_inverse(P, M.reshape(-1, K, T).contiguous(), flags)
     return out.reshape(*lead, P.shape[0], T)
+
+
+# ================================================================ Janssen
+def janssen(sol, n, gap_start, gap_len, p, maxit, return_history=False):
+    """ainp_janssen: gap-wise Janssen AR inpainting of a batch of segments,
+    float64, one workgroup per segment for all maxit iterations.  sol
+    [n_segments, stride] float64 cuda, updated in place (row i: n[i] samples,
+    its gap [gap_start[i], gap_start[i] + gap_len[i]) is zeroed first).  n,
+    gap_start, gap_len: host integers per segment, checked here.  Returns
+    (iters_done int32 [n_segments], history [n_segments, maxit, max gap_len]
+    float64 or None; NaN where an iteration was not completed)."""
+    from . import janssen as _jn
+    _req(sol, "sol", dtype=torch.float64)
+    if sol.dim() != 2:
+        raise ValueError("sol must be [n_segments, stride]")
+    _jn.check_args(p, maxit)
+    nseg, stride = sol.shape
+    tabs = [np.asarray(t, dtype=np.int64).reshape(-1) for t in (n, gap_start, gap_len)]
+    if any(t.size != nseg for t in tabs):
+        raise ValueError("n, gap_start and gap_len need one entry per segment")
+    nn, gs, gl = tabs
+    if nseg and not (np.all(nn > p) and np.all(nn <= min(stride, _jn.N_MAX))):
+        raise ValueError(f"every segment length must be in (p, min(stride, {_jn.N_MAX})]")
+    if nseg and not (np.all(gl >= 1) and np.all(gl <= _jn.GAP_MAX) and np.all(gs >= 0)
+                     and np.all(gs + gl <= nn)):
+        raise ValueError(f"every gap must lie inside its segment, 1 <= gap_len <= {_jn.GAP_MAX}")
+    dev_i32 = [torch.from_numpy(t.astype(np.int32)).to(sol.device) for t in tabs]
+    iters = torch.zeros(nseg, device=sol.device, dtype=torch.int32)
+    hist = None
+    if return_history:
+        hist = torch.full((nseg, int(maxit), int(gl.max()) if nseg else 0), float("nan"),
+                          device=sol.device, dtype=torch.float64)
+    ws_bytes = _lib.lib.ainp_janssen_workspace(nseg, int(nn.max()) if nseg else 0, int(p),
+                                               int(gl.max()) if nseg else 0)
+    ws = torch.empty(ws_bytes, device=sol.device, dtype=torch.uint8) if ws_bytes else None
+    if nseg:
+        _T.janssen(sol, *dev_i32, int(p), int(maxit), hist, iters, ws)
+    return iters, hist

@@ -209,6 +209,40 @@ void mel_inverse(const Tensor& pinv, const Tensor& mel, int64_t flags, const Ten
       "mel_inverse");
 }
 
+// ---------------------------------------------------------------- Janssen
+void janssen(const Tensor& sol, const Tensor& n, const Tensor& gap_start, const Tensor& gap_len,
+             int64_t p, int64_t maxit, const OptT& history, const Tensor& iters_done,
+             const OptT& workspace) {
+  GUARD(sol);
+  TORCH_CHECK(sol.dim() == 2, "sol must be [n_segments, stride]");
+  const int64_t n_seg = sol.size(0);
+  double* x = dev<double>(sol, "sol", at::kDouble);
+  numel_is(n, n_seg, "n");
+  numel_is(gap_start, n_seg, "gap_start");
+  numel_is(gap_len, n_seg, "gap_len");
+  numel_is(iters_done, n_seg, "iters_done");
+  same_device(sol, n);
+  same_device(sol, gap_start);
+  same_device(sol, gap_len);
+  same_device(sol, iters_done);
+  TORCH_CHECK(p >= 1 && p <= INT32_MAX && maxit >= 1 && maxit <= INT32_MAX,
+              "p and maxit must be positive");
+  double* h = opt<double>(history, "history", at::kDouble);
+  if (h) {
+    same_device(sol, *history);
+    TORCH_CHECK(history->dim() == 3 && history->size(0) == n_seg && history->size(1) == maxit,
+                "history must be [n_segments, maxit, max gap_len], got ", history->sizes());
+  }
+  uint8_t* ws = opt<uint8_t>(workspace, "workspace", at::kByte);
+  if (ws) same_device(sol, *workspace);
+  chk(ainp_janssen(x, n_seg, sol.size(1), dev<int32_t>(n, "n", at::kInt),
+                   dev<int32_t>(gap_start, "gap_start", at::kInt),
+                   dev<int32_t>(gap_len, "gap_len", at::kInt), (int)p, (int)maxit, h,
+                   dev<int32_t>(iters_done, "iters_done", at::kInt), ws,
+                   ws ? (size_t)workspace->numel() : 0, stream_of(sol)),
+      "janssen");
+}
+
 // ------------------------------------------------------------------- GEMM
 void gemm(int64_t M, int64_t N, int64_t K, double alpha, at::TensorList A, int64_t sam,
           int64_t sak, int64_t strideA, at::TensorList B, int64_t sbk, int64_t sbn,
@@ -1832,6 +1866,8 @@ TORCH_LIBRARY(ainp, m) {
   m.def("mel_fwd(Tensor spec, Tensor band_lo, Tensor band_off, Tensor weights, float power, "
         "Tensor(a!) out) -> ()");
   m.def("mel_inverse(Tensor pinv, Tensor mel, int flags, Tensor(a!) out) -> ()");
+  m.def("janssen(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int maxit, "
+        "Tensor(b!)? history, Tensor(c!) iters_done, Tensor? workspace) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
@@ -1918,6 +1954,7 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("conv_weight_flip_t", &conv_weight_flip_t);
   m.impl("mel_fwd", &mel_fwd);
   m.impl("mel_inverse", &mel_inverse);
+  m.impl("janssen", &janssen);
 }
 
 // The ops write through raw device pointers like the C ABI; autograd is the
@@ -2007,4 +2044,5 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("conv_weight_flip_t", torch::CppFunction::makeFallthrough());
   m.impl("mel_fwd", torch::CppFunction::makeFallthrough());
   m.impl("mel_inverse", torch::CppFunction::makeFallthrough());
+  m.impl("janssen", torch::CppFunction::makeFallthrough());
 }

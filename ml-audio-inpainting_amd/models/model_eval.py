@@ -17,6 +17,10 @@ Follows models/model_eval.py:23-227 step by step, on the MI355X kernels:
                 spectrogram_to_audio(..., phase=original phase) (:174-191);
                     -> save_audio (peak-normalised FLAC, native encoder)
   run_evaluation  (:198-227) every .flac of input_dir -> <name>_<type>_inpainted.flac
+  run_janssen_evaluation    the same clips and gap through the autoregressive
+                            baseline (models/AudioReg; the third row of
+                            models/AudioReg/model_eval.m's SDR table) ->
+                            <name>_janssen_inpainted.flac and the gap SDRs
 Spectrogram plots (:157-162,180-185) are out of scope (plotting).  The ISTFT
 runs on the GPU (ainp_istft); output length hop * (T - 1), as librosa's.
 """
@@ -150,6 +154,38 @@ def run_evaluation(input_dir, output_dir, model_type, checkpoint, config_path):
         inpaint(model, config_path, os.path.join(input_dir, filename), out, device)
         outs.append(out)
     return outs
+
+
+def run_janssen_evaluation(input_dir, output_dir, p=512, w=4096, maxit=20):
+    """The AR baseline on the clips and the gap of inpaint(): every .flac of
+    input_dir gets the 80 ms gap at 2.0 s, all gaps are filled in one batch by
+    the Janssen algorithm in the time domain, and each result is written as
+    <stem>_janssen_inpainted.flac.  Returns {filename: gap SDR in dB}
+    (models/AudioReg/model_eval.m:60), measured before save_audio's
+    normalisation and 16-bit quantisation."""
+    from models.AudioReg import gap_sdr, janssen_inpaint
+    if not os.path.isdir(input_dir):
+        print(f"Error: Input directory not found: {input_dir}")
+        return
+    os.makedirs(output_dir, exist_ok=True)
+    if not torch.cuda.is_available():
+        raise RuntimeError("model_eval runs on the MI355X kernels: no GPU visible")
+    flac_files = sorted(f for f in os.listdir(input_dir) if f.lower().endswith(".flac"))
+    print(f"Found {len(flac_files)} .flac files in {input_dir}")
+    clean, masks, srs = [], [], []
+    for filename in flac_files:
+        audio, sr = utils.load_audio(os.path.join(input_dir, filename))
+        mask_td, _ = utils.create_gap_mask(len(audio), GAP_LEN_S, sr, gap_start_s=GAP_START_S)
+        clean.append(audio.astype(np.float64))
+        masks.append(mask_td > 0)
+        srs.append(sr)
+    restored = janssen_inpaint(clean, masks, p=p, w=w, maxit=maxit) if clean else []
+    sdrs = {}
+    for filename, x, y, m, sr in zip(flac_files, clean, restored, masks, srs):
+        out = os.path.join(output_dir, f"{os.path.splitext(filename)[0]}_janssen_inpainted.flac")
+        utils.save_audio(y, file_path=out, sample_rate=sr)
+        sdrs[filename] = gap_sdr(x, y, m)
+    return sdrs
 
 
 if __name__ == "__main__":
