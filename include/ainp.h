@@ -195,6 +195,59 @@ int ainp_janssen(double* sol, int64_t n_segments, int64_t stride, const int32_t*
                  void* stream);
 size_t ainp_janssen_workspace(int64_t n_segments, int n_max, int p, int gap_max);
 
+/* The AR estimator of the two baselines, train.m's `method`.  AINP_AR_LPC:
+ * MATLAB lpc (biased autocorrelation + Levinson-Durbin).  AINP_AR_BURG: MATLAB
+ * arburg for real input -- ef = x[1:], eb = x[:-1], and for m = 1..p:
+ * k = -2 sum(eb ef) / (sum(ef^2) + sum(eb^2)), (ef, eb) <- (ef + k eb,
+ * eb + k ef) from the old values, ef loses its first and eb its last element,
+ * a <- [a, 0] + k [0, reverse(a)].  The two error vectors stay in registers
+ * (1024 lanes x 16 elements each), one barrier per step, fixed-order sums. */
+#define AINP_AR_LPC 0
+#define AINP_AR_BURG 1
+
+/* ainp_janssen with the estimator chosen: with AINP_AR_BURG steps 1-2 of the
+ * iteration (autocorrelation + Levinson-Durbin) are the Burg fit of the current
+ * solution; the rest, every argument, the supported range and iters_done are
+ * those of ainp_janssen, which forwards here with AINP_AR_LPC (and whose
+ * messages therefore name ainp_janssen_ex).  With Burg a segment also stops
+ * (iters_done = iterations completed, 0 for a silent context) when a
+ * denominator is not positive and finite or k is not finite.  An unknown
+ * method is AINP_EINVAL.  workspace: at least ainp_janssen_ex_workspace(...)
+ * bytes; 0 for both estimators today. */
+int ainp_janssen_ex(double* sol, int64_t n_segments, int64_t stride, const int32_t* n,
+                    const int32_t* gap_start, const int32_t* gap_len, int p, int maxit,
+                    double* history, int32_t* iters_done, void* workspace,
+                    size_t workspace_bytes, int method, void* stream);
+size_t ainp_janssen_ex_workspace(int64_t n_segments, int n_max, int p, int gap_max, int method);
+
+/* Forward/backward AR extrapolation of one gap per segment, the `extrapolation`
+ * row of the same comparison (models/AudioReg/utils/arinpaint.m).  Float64.
+ * sol, n, gap_start, gap_len as for ainp_janssen; the gap's content on entry is
+ * ignored, observed samples are never written.  pre = the min(gap_start, w)
+ * samples before the gap, post = the time-reversed min(n - gap_start - gap_len,
+ * w) samples after it.  Each side: subtract its mean, fit a[0..p] with the
+ * estimator, run y[t] = -sum_{k=1..p} a[k] y[t-k] for gap_len steps from the
+ * context as the past, add the mean back.  gap = wts * prediction + (1 - wts) *
+ * reverse(postdiction), wts = cos^2(linspace(0, pi/2, gap_len)); for gap_len = 1
+ * the angle is pi/2 (MATLAB's linspace) and the sample is the postdiction.
+ * status int32 [n_segments]: 1 filled; 0 filled, but one side's context was
+ * constant (zero after mean removal; MATLAB's lpc gives NaN there) or its fit
+ * stopped on a non-finite value, and that side predicted its mean; -1 left
+ * untouched because its table entries are outside the supported range.
+ * Supported: 1 <= p <= 3072, both contexts longer than p, n[i] <= min(stride,
+ * 16384), 1 <= gap_len[i] <= 2048 inside the segment, w >= 1.  One workgroup
+ * per side of a segment, then a second launch that blends the two; fixed-order
+ * sums, no atomics: the same bits on every call.  workspace (device): the two
+ * sides meet there.  The tables are on the device, so the launch sizes it by
+ * the stride alone: at least ainp_ar_extrapolate_workspace(n_segments,
+ * min(stride, 16384), p, 2048, method) bytes = n_segments * 2 * (min(stride,
+ * 2048) * 8 + 4). */
+int ainp_ar_extrapolate(double* sol, int64_t n_segments, int64_t stride, const int32_t* n,
+                        const int32_t* gap_start, const int32_t* gap_len, int p, int w, int method,
+                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+size_t ainp_ar_extrapolate_workspace(int64_t n_segments, int n_max, int p, int gap_max,
+                                     int method);
+
 /* ------------------------------------------------------------------------ */
 /* fp32 GEMM on MFMA (fp32-accurate bf16 split by default, exact f32 on flag) */
 /* ------------------------------------------------------------------------ */

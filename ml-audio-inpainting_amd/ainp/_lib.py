@@ -232,6 +232,13 @@ _SIGS = {
     # Janssen autoregressive gap inpainting (csrc/janssen.hip)
     "ainp_janssen": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "ainp_janssen_workspace": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "ainp_janssen_ex": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, P, P, P, c_size_t,
+                                c_int, P]),
+    "ainp_janssen_ex_workspace": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    # forward/backward AR extrapolation (csrc/ar_extrapolate.hip)
+    "ainp_ar_extrapolate": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, c_int, P, P,
+                                    c_size_t, P]),
+    "ainp_ar_extrapolate_workspace": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
 }
 
 EXPORTED = tuple(_SIGS)

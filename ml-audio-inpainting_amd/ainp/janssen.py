@@ -1,9 +1,11 @@
-"""Host side of the Janssen autoregressive baseline (models/AudioReg of the
-reference: utils/janssen_inp.m driven by train.m, method "lpc").
+"""Host side of the autoregressive baselines (models/AudioReg of the
+reference: utils/janssen_inp.m and utils/arinpaint.m driven by train.m, with
+method "lpc" or "arburg").
 
 train.m cuts one segment of w samples either side of every gap and hands each
 to janssen_inp; here every gap of every signal becomes one row of a batch and
-the whole batch is one launch of ainp_janssen (csrc/janssen.hip, float64).
+the whole batch is one launch of ainp_janssen_ex (csrc/janssen.hip, float64)
+or of ainp_ar_extrapolate (csrc/ar_extrapolate.hip).
 Segments are clipped to the signal (train.m:134-135 indexes past the ends for
 a gap within w of them).  gap_sdr is train.m:196 / model_eval.m:60.
 """
@@ -17,6 +19,15 @@ P_MAX = 3072          # csrc/janssen.hip JN_PMAX
 N_MAX = 16384         # JN_NMAX
 GAP_MAX = 2048        # JN_HMAX
 MAXIT_MAX = 1000      # JN_ITMAX
+METHODS = {"lpc": 0, "arburg": 1}     # AINP_AR_LPC, AINP_AR_BURG
+
+
+def method_id(method):
+    """train.m's `method` ("lpc" | "arburg", any case as strcmpi) -> the ABI's id."""
+    key = method.lower() if isinstance(method, str) else method
+    if key not in METHODS:
+        raise ValueError(f"method must be one of {sorted(METHODS)}, got {method!r}")
+    return METHODS[key]
 
 
 @dataclass
@@ -119,8 +130,17 @@ def check_args(p, maxit):
         raise ValueError(f"maxit must be in [1, {MAXIT_MAX}]")
 
 
+def _batch(sigs, seg):
+    """One zero-padded float64 row per segment."""
+    batch = np.zeros((len(seg), int(seg.n.max())), np.float64)
+    for r in range(len(seg)):
+        s = sigs[seg.signal[r]]
+        batch[r, :seg.n[r]] = s[seg.lo[r]:seg.lo[r] + seg.n[r]]
+    return batch
+
+
 def janssen_inpaint(signal, mask=None, p=512, w=4096, maxit=20, return_history=False,
-                    device="cuda"):
+                    device="cuda", method="lpc"):
     """Fill every gap of `signal` by the gap-wise Janssen algorithm on the GPU.
 
     signal: 1-D, a list of 1-D signals, or a 2-D batch (numpy or torch).  mask:
@@ -129,22 +149,19 @@ def janssen_inpaint(signal, mask=None, p=512, w=4096, maxit=20, return_history=F
     input; observed samples come back unchanged.  return_history: also a list
     with one dict per gap (signal, start, end, iters, history [maxit, gap_len]:
     the gap after every iteration, NaN for iterations not completed).
+    method: the AR estimator, "lpc" or "arburg" (train.m's `method`).
     """
     import torch
     from . import ops
     check_args(p, maxit)
+    method_id(method)
     sigs, masks, kind = _normalise(signal, mask)
     seg = plan_segments(masks, w, p)
     info = []
     if len(seg):
-        stride = int(seg.n.max())
-        batch = np.zeros((len(seg), stride), np.float64)
-        for r in range(len(seg)):
-            s = sigs[seg.signal[r]]
-            batch[r, :seg.n[r]] = s[seg.lo[r]:seg.lo[r] + seg.n[r]]
-        sol = torch.from_numpy(batch).to(device)
+        sol = torch.from_numpy(_batch(sigs, seg)).to(device)
         iters, hist = ops.janssen(sol, seg.n, seg.gap_start, seg.gap_len, p, maxit,
-                                  return_history=return_history)
+                                  return_history=return_history, method=method)
         sol, iters = sol.cpu().numpy(), iters.cpu().numpy()
         hist = hist.cpu().numpy() if hist is not None else None
         for r in range(len(seg)):
@@ -156,6 +173,45 @@ def janssen_inpaint(signal, mask=None, p=512, w=4096, maxit=20, return_history=F
                          "history": hist[r, :, :h].copy() if hist is not None else None})
     out = sigs[0] if kind == "single" else sigs if kind == "list" else np.stack(sigs)
     return (out, info) if return_history else out
+
+
+def ar_extrapolate(signal, mask=None, p=512, w=4096, method="lpc", return_status=False,
+                   device="cuda"):
+    """Fill every gap of `signal` by forward/backward AR extrapolation on the
+    GPU (the reference's arinpaint.m): the at most w samples before the gap are
+    predicted forwards, those after it backwards, and the two are cross-faded
+    with cos^2 weights.  Input layouts, mask / NaN conventions and the return
+    layout are janssen_inpaint's.  Both contexts (clipped to the signal and to
+    w) must be longer than p and free of other gaps.  return_status: also a
+    list with one dict per gap (signal, start, end, status: 1, or 0 when a side
+    had a constant context and predicted its mean).
+    """
+    import torch
+    from . import ops
+    check_args(p, 1)
+    method_id(method)
+    sigs, masks, kind = _normalise(signal, mask)
+    seg = plan_segments(masks, w, p)
+    for r in range(len(seg)):
+        pre, post = int(seg.gap_start[r]), int(seg.n[r] - seg.gap_start[r] - seg.gap_len[r])
+        if min(pre, post) <= p:
+            a = int(seg.lo[r] + seg.gap_start[r])
+            raise ValueError(f"signal {seg.signal[r]}: the gap [{a}, {a + int(seg.gap_len[r])}) "
+                             f"has contexts of {pre} and {post} samples, both need more than "
+                             f"p = {p}")
+    info = []
+    if len(seg):
+        sol = torch.from_numpy(_batch(sigs, seg)).to(device)
+        status = ops.ar_extrapolate(sol, seg.n, seg.gap_start, seg.gap_len, p, w, method=method)
+        sol, status = sol.cpu().numpy(), status.cpu().numpy()
+        for r in range(len(seg)):
+            a, h = int(seg.gap_start[r]), int(seg.gap_len[r])
+            lo = int(seg.lo[r])
+            sigs[seg.signal[r]][lo + a:lo + a + h] = sol[r, a:a + h]
+            info.append({"signal": int(seg.signal[r]), "start": lo + a, "end": lo + a + h,
+                         "status": int(status[r])})
+    out = sigs[0] if kind == "single" else sigs if kind == "list" else np.stack(sigs)
+    return (out, info) if return_status else out
 
 
 def gap_sdr(clean, restored, mask):

@@ -2135,19 +2135,13 @@ def mel_to_linear(M, sr=22050, n_fft=2048, n_mels=128, fmin=0.0, fmax=None, powe
 
 
 # ================================================================ Janssen
-def janssen(sol, n, gap_start, gap_len, p, maxit, return_history=False):
-    """ainp_janssen: gap-wise Janssen AR inpainting of a batch of segments,
-    float64, one workgroup per segment for all maxit iterations.  sol
-    [n_segments, stride] float64 cuda, updated in place (row i: n[i] samples,
-    its gap [gap_start[i], gap_start[i] + gap_len[i]) is zeroed first).  n,
-    gap_start, gap_len: host integers per segment, checked here.  Returns
-    (iters_done int32 [n_segments], history [n_segments, maxit, max gap_len]
-    float64 or None; NaN where an iteration was not completed)."""
+def _ar_tables(sol, n, gap_start, gap_len, p):
+    """The host checks the two AR launches share -> (nseg, stride, [n, gap_start,
+    gap_len] as int64 numpy)."""
     from . import janssen as _jn
     _req(sol, "sol", dtype=torch.float64)
     if sol.dim() != 2:
         raise ValueError("sol must be [n_segments, stride]")
-    _jn.check_args(p, maxit)
     nseg, stride = sol.shape
     tabs = [np.asarray(t, dtype=np.int64).reshape(-1) for t in (n, gap_start, gap_len)]
     if any(t.size != nseg for t in tabs):
@@ -2158,15 +2152,59 @@ def janssen(sol, n, gap_start, gap_len, p, maxit, return_history=False):
     if nseg and not (np.all(gl >= 1) and np.all(gl <= _jn.GAP_MAX) and np.all(gs >= 0)
                      and np.all(gs + gl <= nn)):
         raise ValueError(f"every gap must lie inside its segment, 1 <= gap_len <= {_jn.GAP_MAX}")
+    return nseg, stride, tabs
+
+
+def janssen(sol, n, gap_start, gap_len, p, maxit, return_history=False, method="lpc"):
+    """ainp_janssen_ex: gap-wise Janssen AR inpainting of a batch of segments,
+    float64, one workgroup per segment for all maxit iterations.  sol
+    [n_segments, stride] float64 cuda, updated in place (row i: n[i] samples,
+    its gap [gap_start[i], gap_start[i] + gap_len[i]) is zeroed first).  n,
+    gap_start, gap_len: host integers per segment, checked here.  method: the
+    AR estimator, "lpc" or "arburg".  Returns (iters_done int32 [n_segments],
+    history [n_segments, maxit, max gap_len] float64 or None; NaN where an
+    iteration was not completed)."""
+    from . import janssen as _jn
+    _jn.check_args(p, maxit)
+    m = _jn.method_id(method)
+    nseg, stride, tabs = _ar_tables(sol, n, gap_start, gap_len, p)
+    nn, gs, gl = tabs
     dev_i32 = [torch.from_numpy(t.astype(np.int32)).to(sol.device) for t in tabs]
     iters = torch.zeros(nseg, device=sol.device, dtype=torch.int32)
     hist = None
     if return_history:
         hist = torch.full((nseg, int(maxit), int(gl.max()) if nseg else 0), float("nan"),
                           device=sol.device, dtype=torch.float64)
-    ws_bytes = _lib.lib.ainp_janssen_workspace(nseg, int(nn.max()) if nseg else 0, int(p),
-                                               int(gl.max()) if nseg else 0)
+    ws_bytes = _lib.lib.ainp_janssen_ex_workspace(nseg, int(nn.max()) if nseg else 0, int(p),
+                                                  int(gl.max()) if nseg else 0, m)
     ws = torch.empty(ws_bytes, device=sol.device, dtype=torch.uint8) if ws_bytes else None
     if nseg:
-        _T.janssen(sol, *dev_i32, int(p), int(maxit), hist, iters, ws)
+        _T.janssen(sol, *dev_i32, int(p), int(maxit), hist, iters, ws, m)
     return iters, hist
+
+
+def ar_extrapolate(sol, n, gap_start, gap_len, p, w, method="lpc"):
+    """ainp_ar_extrapolate: forward/backward AR extrapolation of one gap per
+    segment (the reference's arinpaint.m), float64.  sol [n_segments, stride]
+    float64 cuda, the gaps filled in place; tables as for janssen.  Each side's
+    context is at most w samples and must be longer than p.  method: "lpc" or
+    "arburg".  Returns status int32 [n_segments]: 1 filled, 0 filled with a
+    side that had a constant context and predicted its mean."""
+    from . import janssen as _jn
+    _jn.check_args(p, 1)
+    if int(w) < 1:
+        raise ValueError("w must be positive")
+    m = _jn.method_id(method)
+    nseg, stride, tabs = _ar_tables(sol, n, gap_start, gap_len, p)
+    nn, gs, gl = tabs
+    if nseg and not (np.all(np.minimum(gs, w) > p) and np.all(np.minimum(nn - gs - gl, w) > p)):
+        raise ValueError("both contexts of every gap (clipped to w) must be longer than p")
+    dev_i32 = [torch.from_numpy(t.astype(np.int32)).to(sol.device) for t in tabs]
+    status = torch.zeros(nseg, device=sol.device, dtype=torch.int32)
+    # the launch sizes its scratch by the stride alone (the tables are on the device)
+    ws_bytes = _lib.lib.ainp_ar_extrapolate_workspace(nseg, min(stride, _jn.N_MAX), int(p),
+                                                      _jn.GAP_MAX, m)
+    ws = torch.empty(ws_bytes, device=sol.device, dtype=torch.uint8) if ws_bytes else None
+    if nseg:
+        _T.ar_extrapolate(sol, *dev_i32, int(p), int(w), m, status, ws)
+    return status

@@ -212,9 +212,11 @@ void mel_inverse(const Tensor& pinv, const Tensor& mel, int64_t flags, const Ten
 // ---------------------------------------------------------------- Janssen
 void janssen(const Tensor& sol, const Tensor& n, const Tensor& gap_start, const Tensor& gap_len,
              int64_t p, int64_t maxit, const OptT& history, const Tensor& iters_done,
-             const OptT& workspace) {
+             const OptT& workspace, int64_t method) {
   GUARD(sol);
   TORCH_CHECK(sol.dim() == 2, "sol must be [n_segments, stride]");
+  TORCH_CHECK(method == AINP_AR_LPC || method == AINP_AR_BURG,
+              "method must be 0 (lpc) or 1 (arburg)");
   const int64_t n_seg = sol.size(0);
   double* x = dev<double>(sol, "sol", at::kDouble);
   numel_is(n, n_seg, "n");
@@ -235,12 +237,40 @@ void janssen(const Tensor& sol, const Tensor& n, const Tensor& gap_start, const 
   }
   uint8_t* ws = opt<uint8_t>(workspace, "workspace", at::kByte);
   if (ws) same_device(sol, *workspace);
-  chk(ainp_janssen(x, n_seg, sol.size(1), dev<int32_t>(n, "n", at::kInt),
-                   dev<int32_t>(gap_start, "gap_start", at::kInt),
-                   dev<int32_t>(gap_len, "gap_len", at::kInt), (int)p, (int)maxit, h,
-                   dev<int32_t>(iters_done, "iters_done", at::kInt), ws,
-                   ws ? (size_t)workspace->numel() : 0, stream_of(sol)),
+  chk(ainp_janssen_ex(x, n_seg, sol.size(1), dev<int32_t>(n, "n", at::kInt),
+                      dev<int32_t>(gap_start, "gap_start", at::kInt),
+                      dev<int32_t>(gap_len, "gap_len", at::kInt), (int)p, (int)maxit, h,
+                      dev<int32_t>(iters_done, "iters_done", at::kInt), ws,
+                      ws ? (size_t)workspace->numel() : 0, (int)method, stream_of(sol)),
       "janssen");
+}
+
+void ar_extrapolate(const Tensor& sol, const Tensor& n, const Tensor& gap_start,
+                    const Tensor& gap_len, int64_t p, int64_t w, int64_t method,
+                    const Tensor& status, const OptT& workspace) {
+  GUARD(sol);
+  TORCH_CHECK(sol.dim() == 2, "sol must be [n_segments, stride]");
+  TORCH_CHECK(method == AINP_AR_LPC || method == AINP_AR_BURG,
+              "method must be 0 (lpc) or 1 (arburg)");
+  const int64_t n_seg = sol.size(0);
+  double* x = dev<double>(sol, "sol", at::kDouble);
+  numel_is(n, n_seg, "n");
+  numel_is(gap_start, n_seg, "gap_start");
+  numel_is(gap_len, n_seg, "gap_len");
+  numel_is(status, n_seg, "status");
+  same_device(sol, n);
+  same_device(sol, gap_start);
+  same_device(sol, gap_len);
+  same_device(sol, status);
+  TORCH_CHECK(p >= 1 && p <= INT32_MAX && w >= 1 && w <= INT32_MAX, "p and w must be positive");
+  uint8_t* ws = opt<uint8_t>(workspace, "workspace", at::kByte);
+  if (ws) same_device(sol, *workspace);
+  chk(ainp_ar_extrapolate(x, n_seg, sol.size(1), dev<int32_t>(n, "n", at::kInt),
+                          dev<int32_t>(gap_start, "gap_start", at::kInt),
+                          dev<int32_t>(gap_len, "gap_len", at::kInt), (int)p, (int)w, (int)method,
+                          dev<int32_t>(status, "status", at::kInt), ws,
+                          ws ? (size_t)workspace->numel() : 0, stream_of(sol)),
+      "ar_extrapolate");
 }
 
 // ------------------------------------------------------------------- GEMM
@@ -1867,7 +1897,9 @@ TORCH_LIBRARY(ainp, m) {
         "Tensor(a!) out) -> ()");
   m.def("mel_inverse(Tensor pinv, Tensor mel, int flags, Tensor(a!) out) -> ()");
   m.def("janssen(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int maxit, "
-        "Tensor(b!)? history, Tensor(c!) iters_done, Tensor? workspace) -> ()");
+        "Tensor(b!)? history, Tensor(c!) iters_done, Tensor? workspace, int method=0) -> ()");
+  m.def("ar_extrapolate(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int w, "
+        "int method, Tensor(b!) status, Tensor? workspace) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
@@ -1955,6 +1987,7 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("mel_fwd", &mel_fwd);
   m.impl("mel_inverse", &mel_inverse);
   m.impl("janssen", &janssen);
+  m.impl("ar_extrapolate", &ar_extrapolate);
 }
 
 // The ops write through raw device pointers like the C ABI; autograd is the
@@ -2045,4 +2078,5 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("mel_fwd", torch::CppFunction::makeFallthrough());
   m.impl("mel_inverse", torch::CppFunction::makeFallthrough());
   m.impl("janssen", torch::CppFunction::makeFallthrough());
+  m.impl("ar_extrapolate", torch::CppFunction::makeFallthrough());
 }

@@ -21,6 +21,8 @@ Follows models/model_eval.py:23-227 step by step, on the MI355X kernels:
                             baseline (models/AudioReg; the third row of
                             models/AudioReg/model_eval.m's SDR table) ->
                             <name>_janssen_inpainted.flac and the gap SDRs
+  run_ar_evaluation         any cell of models/AudioReg/train.m's table: Janssen
+                            or forward/backward extrapolation, "lpc" or "arburg"
 Spectrogram plots (:157-162,180-185) are out of scope (plotting).  The ISTFT
 runs on the GPU (ainp_istft); output length hop * (T - 1), as librosa's.
 """
@@ -183,6 +185,49 @@ def run_janssen_evaluation(input_dir, output_dir, p=512, w=4096, maxit=20):
     sdrs = {}
     for filename, x, y, m, sr in zip(flac_files, clean, restored, masks, srs):
         out = os.path.join(output_dir, f"{os.path.splitext(filename)[0]}_janssen_inpainted.flac")
+        utils.save_audio(y, file_path=out, sample_rate=sr)
+        sdrs[filename] = gap_sdr(x, y, m)
+    return sdrs
+
+
+def run_ar_evaluation(input_dir, output_dir, algorithm="janssen", method="lpc", p=512, w=4096,
+                      maxit=20):
+    """One cell of models/AudioReg/train.m's table on the clips and the gap of
+    inpaint(): algorithm "janssen" or "extrapolation", estimator "lpc" or
+    "arburg".  Every .flac of input_dir gets the 80 ms gap at 2.0 s, all gaps
+    are filled in one batch, and each result is written as
+    <stem>_<algorithm>[_arburg]_inpainted.flac.  Returns {filename: gap SDR in
+    dB}, measured before save_audio's normalisation and 16-bit quantisation.
+    maxit applies to "janssen" only."""
+    from models.AudioReg import ar_extrapolate, gap_sdr, janssen_inpaint
+    from ainp.janssen import method_id
+    if algorithm not in ("janssen", "extrapolation"):
+        raise ValueError(f"algorithm must be 'janssen' or 'extrapolation', got {algorithm!r}")
+    suffix = algorithm + ("_arburg" if method_id(method) else "")
+    if not os.path.isdir(input_dir):
+        print(f"Error: Input directory not found: {input_dir}")
+        return
+    os.makedirs(output_dir, exist_ok=True)
+    if not torch.cuda.is_available():
+        raise RuntimeError("model_eval runs on the MI355X kernels: no GPU visible")
+    flac_files = sorted(f for f in os.listdir(input_dir) if f.lower().endswith(".flac"))
+    print(f"Found {len(flac_files)} .flac files in {input_dir}")
+    clean, masks, srs = [], [], []
+    for filename in flac_files:
+        audio, sr = utils.load_audio(os.path.join(input_dir, filename))
+        mask_td, _ = utils.create_gap_mask(len(audio), GAP_LEN_S, sr, gap_start_s=GAP_START_S)
+        clean.append(audio.astype(np.float64))
+        masks.append(mask_td > 0)
+        srs.append(sr)
+    if not clean:
+        restored = []
+    elif algorithm == "janssen":
+        restored = janssen_inpaint(clean, masks, p=p, w=w, maxit=maxit, method=method)
+    else:
+        restored = ar_extrapolate(clean, masks, p=p, w=w, method=method)
+    sdrs = {}
+    for filename, x, y, m, sr in zip(flac_files, clean, restored, masks, srs):
+        out = os.path.join(output_dir, f"{os.path.splitext(filename)[0]}_{suffix}_inpainted.flac")
         utils.save_audio(y, file_path=out, sample_rate=sr)
         sdrs[filename] = gap_sdr(x, y, m)
     return sdrs

@@ -1,10 +1,14 @@
-"""Times ainp_janssen (csrc/janssen.hip) at the reference's configuration
+"""Times ainp_janssen_ex (csrc/janssen.hip) and, with --algorithm
+extrapolation, ainp_ar_extrapolate (csrc/ar_extrapolate.hip) at the reference's
+configuration
 (models/AudioReg/train.m: w = 4096 samples of context either side of an 80 ms
 gap at 16 kHz, h = 1280, 20 iterations) for AR orders p in {256, 512, 1024,
 3072} and batches of 1, 9, 64 and 256 segments, next to a float64 CPU run of
 the same algorithm (FFT autocorrelation, scipy.linalg.solve_toeplitz for the
 AR fit and for the gap -- the fast Toeplitz variant, not the tests' dense
-reference) on `--threads` worker processes, one single-threaded segment each
+reference; --method arburg: Burg's estimator in numpy whole-vector operations;
+--algorithm extrapolation: the fit of either kind per side, scipy.signal's
+lfiltic + lfilter for the recursion) on `--threads` worker processes, one single-threaded segment each
 (solve_toeplitz holds the GIL, so threads of one process would run in turn).
 The workers are started, timed and joined before this process touches the GPU
 and import nothing of torch; `cpu x1` is one worker alone, `cpu xT` the wall
@@ -24,7 +28,13 @@ workgroup.  --fit times batch 1 over p x h in {640, 1280} and fits
 by least squares; it prints both constants, each case's share of the chain
 and the residuals.  Prints one table row and one JSON line per case.
 
+--burg-steps times one Janssen iteration with the Burg estimator and a 16-sample
+gap (so the p Burg steps dominate) at n = 9472 and n = 16384 and prints the
+time per Burg step and its slope between successive orders.
+
 Usage: python tools/janssen_bench.py [--reps 5] [--threads 16] [--no-cpu] [--fit]
+           [--method lpc|arburg] [--algorithm janssen|extrapolation]
+           [--orders 256,512] [--batches 1,256] [--burg-steps]
 """
 import argparse
 import json
@@ -47,18 +57,26 @@ ORDERS = (256, 512, 1024, 3072)
 BATCHES = (1, 9, 64, 256)
 
 
-def cpu_janssen(x, s, h, p, maxit):
+def cpu_fit(x, p, method):
+    """[1, a_1 .. a_p]: FFT autocorrelation + Toeplitz solve, or Burg."""
+    if method == "arburg":
+        from ar_ref import arburg
+        return arburg(x, p)
+    from scipy.linalg import solve_toeplitz
+    nfft = 1 << int(np.ceil(np.log2(2 * len(x) - 1)))
+    r = np.fft.irfft(np.abs(np.fft.rfft(x, nfft)) ** 2, nfft)[:p + 1]
+    return np.concatenate(([1.0], solve_toeplitz(r[:p], -r[1:p + 1])))
+
+
+def cpu_janssen(x, s, h, p, maxit, method="lpc"):
     """The same algorithm in float64 numpy / scipy, Toeplitz solves throughout."""
     from scipy.linalg import solve_toeplitz
     from scipy.signal import fftconvolve
-    n = len(x)
     sol = x.copy()
     sol[s:s + h] = 0.0
     obs = sol.copy()
-    nfft = 1 << int(np.ceil(np.log2(2 * n - 1)))
     for _ in range(maxit):
-        r = np.fft.irfft(np.abs(np.fft.rfft(sol, nfft)) ** 2, nfft)[:p + 1]
-        a = np.concatenate(([1.0], solve_toeplitz(r[:p], -r[1:p + 1])))
+        a = cpu_fit(sol, p, method)
         b = np.correlate(a, a, "full")[p:]
         col = np.zeros(h)
         col[:min(h, p + 1)] = b[:h]
@@ -67,7 +85,23 @@ def cpu_janssen(x, s, h, p, maxit):
     return sol
 
 
-def time_gpu(batch, n, s, h, p, maxit, reps):
+def cpu_extrapolate(x, s, h, p, w, method="lpc"):
+    """arinpaint.m: per side mean, fit, filtic + filter, then the cross-fade."""
+    from scipy.signal import lfilter, lfiltic
+    sol = x.copy()
+    sides = []
+    for c in (x[max(0, s - w):s], x[s + h:min(len(x), s + h + w)][::-1]):
+        mean = c.mean()
+        y = c - mean
+        a = cpu_fit(y, p, method)
+        zi = lfiltic([1.0], a, y[::-1][:p])
+        sides.append(lfilter([1.0], a, np.zeros(h), zi=zi)[0] + mean)
+    wts = np.cos(np.linspace(0.0, np.pi / 2, h)) ** 2
+    sol[s:s + h] = wts * sides[0] + (1.0 - wts) * sides[1][::-1]
+    return sol
+
+
+def time_gpu(batch, n, s, h, p, maxit, reps, method="lpc", algorithm="janssen"):
     import torch
     from ainp import ops
     x0 = torch.from_numpy(np.stack([signal(n, 100 + i) for i in range(min(batch, 16))]))
@@ -79,39 +113,48 @@ def time_gpu(batch, n, s, h, p, maxit, reps):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        iters, _ = ops.janssen(sol, *tabs, p, maxit)
+        if algorithm == "janssen":
+            iters, _ = ops.janssen(sol, *tabs, p, maxit, method=method)
+        else:
+            status = ops.ar_extrapolate(sol, *tabs, p, W, method=method)
         e1.record()
         torch.cuda.synchronize()
         if r:
             ts.append(e0.elapsed_time(e1))          # ms
-    assert int(iters.min()) == maxit, "a segment stopped early"
+    if algorithm == "janssen":
+        assert int(iters.min()) == maxit, "a segment stopped early"
+    else:
+        assert int(status.min()) == 1, "a segment was not filled from both sides"
     return statistics.median(ts), min(ts), max(ts), sol[0].cpu().numpy()
 
 
 def _cpu_job(args):
-    n, seed, s, h, p, maxit = args
-    return cpu_janssen(signal(n, seed), s, h, p, maxit)
+    n, seed, s, h, p, maxit, method, algorithm = args
+    if algorithm == "janssen":
+        return cpu_janssen(signal(n, seed), s, h, p, maxit, method)
+    return cpu_extrapolate(signal(n, seed), s, h, p, W, method)
 
 
-def time_cpu(pool, workers, n, s, h, p, maxit):
+def time_cpu(pool, workers, n, s, h, p, maxit, method, algorithm):
     """ms per segment with `workers` segments in flight (wall / workers)."""
-    jobs = [(n, 100 + i, s, h, p, maxit) for i in range(workers)]
+    jobs = [(n, 100 + i, s, h, p, maxit, method, algorithm) for i in range(workers)]
     t0 = time.perf_counter()
     outs = pool.map(_cpu_job, jobs, chunksize=1)
     return (time.perf_counter() - t0) * 1e3 / workers, outs[0]
 
 
-def cpu_table(n, threads):
+def cpu_table(n, threads, orders, method, algorithm):
     """{p: (ms alone, ms per segment at `threads` in flight, solution)}; runs
     and ends its worker processes before the caller opens the GPU."""
     import multiprocessing as mp
     out = {}
     with mp.get_context("spawn").Pool(threads) as pool:
-        pool.map(_cpu_job, [(n, 100 + i, W, H, 64, 1) for i in range(4 * threads)],
+        pool.map(_cpu_job, [(n, 100 + i, W, H, 64, 1, method, algorithm)
+                            for i in range(4 * threads)],
                  chunksize=1)                       # every worker up: imports, FFT plans
-        for p in ORDERS:
-            one, _ = time_cpu(pool, 1, n, W, H, p, MAXIT)
-            per, sol = time_cpu(pool, threads, n, W, H, p, MAXIT)
+        for p in orders:
+            one, _ = time_cpu(pool, 1, n, W, H, p, MAXIT, method, algorithm)
+            per, sol = time_cpu(pool, threads, n, W, H, p, MAXIT, method, algorithm)
             out[p] = (one, per, sol)
             print(f"cpu p {p:5d}  x1 {one:9.2f} ms/segment  x{threads} {per:9.2f} ms/segment "
                   f"({one / per:.1f} segments at a time)", flush=True)
@@ -130,16 +173,25 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--fit", action="store_true")
+    ap.add_argument("--method", choices=("lpc", "arburg"), default="lpc")
+    ap.add_argument("--algorithm", choices=("janssen", "extrapolation"), default="janssen")
+    ap.add_argument("--orders", type=lambda v: tuple(int(t) for t in v.split(",")), default=ORDERS)
+    ap.add_argument("--batches", type=lambda v: tuple(int(t) for t in v.split(",")),
+                    default=BATCHES)
+    ap.add_argument("--burg-steps", action="store_true")
     args = ap.parse_args()
     n = 2 * W + H
-    cpu = {} if args.no_cpu else cpu_table(n, args.threads)
+    method, algorithm = args.method, args.algorithm
+    cpu = {} if args.no_cpu else cpu_table(n, args.threads, args.orders, method, algorithm)
     import torch
-    print(f"{torch.cuda.get_device_name(0)}; n = {n}, h = {H}, maxit = {MAXIT}", flush=True)
-    for p in ORDERS:
+    print(f"{torch.cuda.get_device_name(0)}; {algorithm} {method}, n = {n}, h = {H}, "
+          f"maxit = {MAXIT}", flush=True)
+    for p in args.orders:
         cpu_one, cpu_ms, cpu_sol = cpu.get(p, (None, None, None))
-        for batch in BATCHES:
-            med, lo, hi, gsol = time_gpu(batch, n, W, H, p, MAXIT, args.reps)
-            row = dict(p=p, batch=batch, launch_ms=round(med, 3), launch_ms_min=round(lo, 3),
+        for batch in args.batches:
+            med, lo, hi, gsol = time_gpu(batch, n, W, H, p, MAXIT, args.reps, method, algorithm)
+            row = dict(algorithm=algorithm, method=method, p=p, batch=batch,
+                       launch_ms=round(med, 3), launch_ms_min=round(lo, 3),
                        launch_ms_max=round(hi, 3), per_segment_ms=round(med / batch, 4),
                        per_iteration_us=round(med * 1e3 / MAXIT, 2))
             line = (f"p {p:5d} batch {batch:4d}  launch {med:9.3f} ms [{lo:9.3f} .. {hi:9.3f}]  "
@@ -155,6 +207,20 @@ def main():
                                                     / np.max(np.abs(gsol[g])))
             print(line, flush=True)
             print(json.dumps(row), flush=True)
+    if args.burg_steps:
+        for nn in (n, 16384):
+            prev = None
+            for p in ORDERS:
+                med, lo, hi, _ = time_gpu(1, nn, nn // 2, 16, p, 1, args.reps, "arburg")
+                slope = None if prev is None else (med - prev[1]) * 1e6 / (p - prev[0])
+                print(f"burg steps n {nn:5d} p {p:5d}  iteration {med * 1e3:9.1f} us "
+                      f"[{lo * 1e3:9.1f} .. {hi * 1e3:9.1f}]  {med * 1e6 / p:7.1f} ns/step"
+                      + ("" if slope is None else f"  slope {slope:7.1f} ns/step"), flush=True)
+                print(json.dumps(dict(burg_steps=True, n=nn, p=p, iteration_us=round(med * 1e3, 1),
+                                      ns_per_step=round(med * 1e6 / p, 1),
+                                      slope_ns_per_step=None if slope is None
+                                      else round(slope, 1))), flush=True)
+                prev = (p, med)
     if args.fit:
         cases = [(p, h) for p in ORDERS for h in (640, 1280)]
         t = np.array([time_gpu(1, n, W, h, p, MAXIT, args.reps)[0] * 1e3 / MAXIT
