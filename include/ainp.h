@@ -874,6 +874,44 @@ int ainp_conv_gen_fwd_nhwc16_ex(const uint16_t* x0, int C0, int H0, int W0, cons
  * previous variant; an out-of-range v only queries.  Initial value: env
  * AINP_CONV16. */
 int ainp_conv16_set_variant(int v);
+/* Which entry point and kernel serve one generic convolution (host only, no
+ * GPU state): the launchers above route through the same table
+ * (csrc/conv_gen_route.h), so a caller that sizes its buffers and picks its
+ * entry point from the plan cannot disagree with them.  The call: sources as
+ * ainp_conv_gen_fwd_out16 takes them (C1 == 0: one source), flags =
+ * AINP_CONV_BF16 or 0, want_stats / want_y16 = BatchNorm partials / the bf16
+ * channel-last copy of y wanted, crop as there.  The caller's policy: nhwc16 =
+ * bf16 convs run on channel-last bf16 operands; nhwc16_small = sources with
+ * C % 32 != 0 there too (0 never, 1 unless the few-input-channel kernel
+ * serves the conv, 2 always); out16 / out16_direct = the conv (the
+ * few-input-channel kernel too) may write the bf16 copy. */
+typedef struct AinpConvGenCall {
+  int64_t N;
+  int C0, H0, W0, C1, H1, W1;
+  int Cout, Hin, Win, KH, KW, stride, pad, crop_h, crop_w;
+  int flags, want_stats, want_y16;
+  int nhwc16, nhwc16_small, out16, out16_direct;
+} AinpConvGenCall;
+/* entry: 0 = ainp_conv_gen_fwd_out16 (NCHW fp32 operands), 1 =
+ * ainp_conv_gen_fwd_nhwc16_ex (channel-last bf16 operands; expand0 / expand1:
+ * that source is passed as ainp_im2col_nhwc16 rows).  kernel: "cout1_loop",
+ * "cout1_taps", "smallcin", "x6", "exact", "nhwc16_tiles", "nhwc16_ring",
+ * "nhwc16_wide"; name: the kernel's name as profiler rows start.  stat_rows:
+ * rows of the stats buffer; workspace: bytes (the Cout == 1 crop included);
+ * y16_ok: the entry point takes y16 on this route.  refusal: NULL, or the
+ * message the entry point will fail with. */
+typedef struct AinpConvGenPlan {
+  int entry, expand0, expand1, nsplit, y16_ok;
+  int64_t stat_rows;
+  size_t workspace;
+  const char* kernel;
+  const char* name;
+  const char* refusal;
+} AinpConvGenPlan;
+int ainp_conv_gen_plan(const AinpConvGenCall* call, AinpConvGenPlan* plan);
+/* k-values a source of C channels spans in a wt16 row / an
+ * ainp_im2col_nhwc16 row for a kernel of KK taps (S above). */
+int ainp_nhwc16_seg(int C, int KK);
 /* PartialConv2d mask update (networks.py:83-104, multi_channel=False):
  * count = C0*window_sum(m0) + C1*window_sum(m1) over the conv's window (masks
  * are planes of integer counts -- 0/1, or a channel sum -- repeated over their

@@ -31,6 +31,23 @@ lib = _load()
 
 P = c_void_p
 PP = POINTER(c_void_p)
+
+
+class ConvGenCall(ctypes.Structure):
+    """AinpConvGenCall (include/ainp.h)."""
+    _fields_ = [("N", c_int64)] + [(n, c_int) for n in (
+        "C0", "H0", "W0", "C1", "H1", "W1", "Cout", "Hin", "Win", "KH", "KW", "stride", "pad",
+        "crop_h", "crop_w", "flags", "want_stats", "want_y16", "nhwc16", "nhwc16_small", "out16",
+        "out16_direct")]
+
+
+class ConvGenPlan(ctypes.Structure):
+    """AinpConvGenPlan (include/ainp.h)."""
+    _fields_ = [(n, c_int) for n in ("entry", "expand0", "expand1", "nsplit", "y16_ok")] + [
+        ("stat_rows", c_int64), ("workspace", c_size_t), ("kernel", c_char_p), ("name", c_char_p),
+        ("refusal", c_char_p)]
+
+
 _SIGS = {
     "ainp_abi_version": (c_int, []),
     "ainp_build_target": (c_char_p, []),
@@ -199,6 +216,8 @@ _SIGS = {
     "ainp_im2col_nhwc16": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                    c_int, c_int, P, P]),
     "ainp_conv16_set_variant": (c_int, [c_int]),
+    "ainp_conv_gen_plan": (c_int, [POINTER(ConvGenCall), POINTER(ConvGenPlan)]),
+    "ainp_nhwc16_seg": (c_int, [c_int, c_int]),
     "ainp_conv_gen_fwd_nhwc16": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P,
                                          P, P, P, c_int64, c_int, c_int, c_int, c_int, c_int,
                                          c_int, c_int, c_int, c_float, P, P]),

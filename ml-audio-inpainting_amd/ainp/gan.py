@@ -183,13 +183,12 @@ AFFINE_NO_Y = os.environ.get("AINP_AFFINE_NO_Y", "1") != "0"
 
 def _affine_no_y_safe():
     """The fp32 write-back may be skipped only while every consumer of a U-Net
-    block output reads the channel-last copy: the 32-multiple-channel convs
-    always take the nhwc16 route, but the final PartialConv2d's (64 + 1 -> 64)
-    second source is the 1-channel padded input, which reaches that route only
-    through the CONV_NHWC16_SMALL branch (ops._nhwc16_route); with
-    AINP_CONV_NHWC16_SMALL=0 it runs the NCHW fp32 gather, which reads the
-    block output's fp32 planes, so they must be written."""
-    return AFFINE_NO_Y and ops.CONV_NHWC16 and ops.CONV_NHWC16_SMALL != "0"
+    block output reads the channel-last copy.  EncoderBlock.run asks that of
+    the convs over the block's own channels; the final PartialConv2d's
+    (64 + 1 -> 64) second source is the 1-channel padded input, and with
+    AINP_CONV_NHWC16_SMALL=0 that conv runs the NCHW fp32 gather, which reads
+    the block output's fp32 planes, so they must be written."""
+    return AFFINE_NO_Y and ops.conv_reads_nhwc16(64, 1, 64)
 
 
 class EncoderBlock(nn.Module):
@@ -222,8 +221,8 @@ class EncoderBlock(nn.Module):
         bf16 path the fp32 block output is not written back -- its consumers
         read the copy."""
         y, newm, stats = self.pconv.run(srcs, Hin, Win, want_stats=self._want_stats())
-        if (self.pconv.ainp_bf16 and ops._NHWC_MEMO is not None and ops.CONV_NHWC16
-                and y.shape[1] % 32 == 0):
+        if (self.pconv.ainp_bf16 and ops._NHWC_MEMO is not None
+                and ops.conv_reads_nhwc16(y.shape[1])):
             # bf16 U-Net: the next conv's channel-last source in the same pass
             N, C, Ho, Wo = y.shape
             if isinstance(self.norm, nn.BatchNorm2d):

@@ -13,6 +13,7 @@ this module fails when libainp_torch.so is missing.  Host-only queries
 from __future__ import annotations
 
 import atexit
+import collections
 import functools
 import heapq
 import itertools
@@ -1225,28 +1226,53 @@ OUT16_DIRECT = os.environ.get("AINP_OUT16_DIRECT", "1") != "0"
 
 
 def nhwc16_seg(C, KK):
-    """k-values a source contributes to an nhwc16 weight row (gan.hip)."""
-    return -(-KK * C // 32) * 32 if C % 32 else KK * C
+    """k-values a source contributes to an nhwc16 weight row (ainp_nhwc16_seg)."""
+    return int(_lib.lib.ainp_nhwc16_seg(int(C), int(KK)))
 
 
-def _direct_route(C0, C1, H0, W0, Hin, Win, KH, KW, Cout, want_stats):
-    """ainp_conv_gen_fwd_ex's few-input-channel kernel (gan.hip
-    conv_gen_smallcin_kernel) takes this conv (AINP_CONV_SMALLCIN unset)."""
-    return (os.environ.get("AINP_CONV_SMALLCIN", "1") != "0" and C1 == 0
-            and (H0, W0) == (Hin, Win) and not want_stats and 1 < Cout <= 64
-            and C0 * KH * KW <= 160 and C0 <= 4)
+ConvGenPlan = collections.namedtuple(
+    "ConvGenPlan", "entry expand0 expand1 nsplit y16_ok stat_rows workspace kernel name refusal")
+# conv_gen_plan's answers per call shape, so a training step's convs do not
+# cross into the library twice each.  The main-loop variant changes `kernel`
+# and `name` (nothing that sizes a buffer): conv16_set_variant clears the memo,
+# a direct _lib.lib.ainp_conv16_set_variant call would leave those two stale.
+_PLANS: dict = {}
 
 
-def _nhwc16_route(C0, C1, H0, W0, Hin, Win, KH, KW, Cout, want_stats):
-    if not CONV_NHWC16:
-        return False
-    if C0 % 32 == 0 and C1 % 32 == 0:
-        return True
-    if CONV_NHWC16_SMALL == "0":
-        return False
-    direct = (C1 == 0 and (H0, W0) == (Hin, Win) and not want_stats and Cout <= 64
-              and C0 * KH * KW <= 160 and C0 <= 4)
-    return CONV_NHWC16_SMALL == "all" or not direct
+def conv_gen_plan(N, C0, H0, W0, C1, H1, W1, Cout, Hin, Win, KH, KW, stride, pad, crop_h=0,
+                  crop_w=0, bf16=False, want_stats=False, want_y16=False):
+    """ainp_conv_gen_plan under this module's switches (CONV_NHWC16,
+    CONV_NHWC16_SMALL, CONV_OUT16, OUT16_DIRECT): the entry point (0 NCHW fp32
+    operands, 1 channel-last bf16 operands; expand0 / expand1: that source as
+    im2col_nhwc16 rows) and kernel that serve the conv (csrc/conv_gen_route.h),
+    its stats rows and workspace bytes, and whether it takes y16."""
+    key = (int(N), int(C0), int(H0), int(W0), int(C1), int(H1), int(W1), int(Cout), int(Hin),
+           int(Win), int(KH), int(KW), int(stride), int(pad), int(crop_h), int(crop_w),
+           CONV_BF16 if bf16 else 0, int(bool(want_stats)), int(bool(want_y16)), int(CONV_NHWC16),
+           {"0": 0, "all": 2}.get(CONV_NHWC16_SMALL, 1), int(CONV_OUT16), int(OUT16_DIRECT))
+    plan = _PLANS.get(key)
+    if plan is None:
+        c = _lib.ConvGenPlan()
+        if _lib.lib.ainp_conv_gen_plan(_lib.ConvGenCall(*key), c):
+            raise _lib.AinpError(_lib.lib.ainp_last_error().decode())
+        plan = _PLANS[key] = ConvGenPlan(
+            c.entry, bool(c.expand0), bool(c.expand1), c.nsplit, bool(c.y16_ok), c.stat_rows,
+            c.workspace, c.kernel.decode(), c.name.decode(),
+            c.refusal.decode() if c.refusal else None)
+    return plan
+
+
+def conv_reads_nhwc16(C, C1=0, Cout=64, k=3):
+    """A bf16 conv_gen over a C-channel source (and a second one of C1
+    channels) reads that source's channel-last bf16 copy (to_nhwc16, the
+    nhwc16_memo), not its fp32 planes.  Callers skip writing those planes on
+    this answer for every consumer of the source, whatever its size, stride or
+    Cout, from this one probe (16 x 16, stride 1): that holds because
+    route_conv_gen decides the entry point and `expand` of a source of whole
+    32-channel tiles from the channel counts and the policy alone.  A gate there
+    that looks at the size or stride must come with a probe per consumer here."""
+    plan = conv_gen_plan(1, C, 16, 16, C1, 16, 16, Cout, 16, 16, k, k, 1, k // 2, bf16=True)
+    return plan.entry == 1 and not plan.expand0
 
 
 def conv_weight_nhwc16(w, C0, C1):
@@ -1310,6 +1336,7 @@ def conv16_set_variant(v):
     register-staged tiles, 1 LDS-DMA ring, 2 / 3 wide-tile ring of 4 / 8 waves
     (3, the default: Cout > 64, else 0); same sums in all, bit for bit.  Returns
     the previous variant (v outside 0..3 only queries)."""
+    _PLANS.clear()
     return int(_lib.lib.ainp_conv16_set_variant(int(v)))
 
 
@@ -1343,23 +1370,15 @@ def conv_gen(src0, w, *, src1=None, Hin=None, Win=None, stride=1, pad=0, bias=No
                 raise ValueError("conv_gen: mask plane must be [N, Hs, Ws] of its source")
     Ho, Wo = conv_out_size(Hin, KH, stride, pad), conv_out_size(Win, KW, stride, pad)
     ch, cw = (0, 0) if crop is None else crop
+    plan = conv_gen_plan(N, C0, H0, W0, C1, H1, W1, Cout, Hin, Win, KH, KW, stride, pad, ch, cw,
+                         bf16, want_stats, out16 and bf16 and _NHWC_MEMO is not None)
+    if plan.refusal:   # what the entry point would answer, before anything is allocated
+        raise _lib.AinpError(plan.refusal)
     if WORK_TRACE is not None and not launcher:
-        flop = 2.0 * N * Cout * Cin * KH * KW * ((ch * cw) if (Cout == 1 and crop) else Ho * Wo)
-        if bf16 and Cout > 1 and crop is None and _nhwc16_route(C0, C1, H0, W0, Hin, Win, KH, KW,
-                                                                 Cout, want_stats):
-            nm = ("conv_gen_nhwc16_wide_kernel<256" if Cout > 128 else
-                  "conv_gen_nhwc16_wide_kernel<128" if Cout > 64 else "conv_gen_nhwc16_kernel<64")
-        elif Cout == 1:
-            # both Cout = 1 kernels: conv_cout1_partial_kernel and the batched-
-            # tap conv_cout1_partial_b_kernel<KT, CG> (round 6)
-            nm = "conv_cout1_partial"
-        elif _direct_route(C0, C1, H0, W0, Hin, Win, KH, KW, Cout, want_stats):
-            nm = "conv_gen_smallcin_kernel"
-        else:
-            # exact kernel names: a bare "conv_gen" would also match the nhwc16,
-            # few-channel, wide and split-K epilogue rows of the step table
-            nm = "conv_gen_x6_kernel" if not bf16 else "conv_gen_fwd_kernel"
-        _work(nm, flop)
+        # the kernel's own name: a bare "conv_gen" would also match the other
+        # routes' and the split-K epilogue's rows of the step table
+        _work(plan.name,
+              2.0 * N * Cout * Cin * KH * KW * ((ch * cw) if (Cout == 1 and crop) else Ho * Wo))
     if out is None:
         if Cout == 1 and crop is not None:
             out = torch.empty(N, ch, cw, device=x0.device, dtype=torch.float32)
@@ -1367,31 +1386,26 @@ def conv_gen(src0, w, *, src1=None, Hin=None, Win=None, stride=1, pad=0, bias=No
             out = torch.empty(N, Cout, Ho, Wo, device=x0.device, dtype=torch.float32)
     stats = None
     if want_stats:
-        parts = _lib.lib.ainp_conv_gen_stat_parts(N, Cin, KH, KW, Cout, Ho, Wo)
-        stats = torch.empty(parts, 2, Cout, device=x0.device, dtype=torch.float64)
+        stats = torch.empty(plan.stat_rows, 2, Cout, device=x0.device, dtype=torch.float64)
     for t, nm in ((bias, "bias"), (ratio, "ratio"), (scale, "scale")):
         if t is not None:
             _req(t, nm)
-    ws = wt = None
-    if bf16 and Cout > 1 and crop is None and _nhwc16_route(C0, C1, H0, W0, Hin, Win, KH, KW,
-                                                             Cout, want_stats):
-        nb = int(_lib.lib.ainp_conv_gen_workspace(N, Cin, KH, KW, Cout, Ho, Wo))
-        if nb:
-            ws = torch.empty(-(-nb // 4), device=x0.device)
-        def src16(x, m, C):
-            if C % 32:   # few channels: expanded per output pixel
+    ws = torch.empty(-(-plan.workspace // 4), device=x0.device) if plan.workspace else None
+    y16 = None
+    if plan.y16_ok:   # the kernel / its epilogue writes the next conv's channel-last source
+        y16 = torch.empty(N, Ho, Wo, Cout, device=x0.device, dtype=torch.bfloat16)
+    if plan.entry == 1:
+        def src16(x, m, C, expand):
+            if expand:   # few channels: expanded per output pixel
                 e = torch.empty(N * Ho * Wo, nhwc16_seg(C, KH * KW), device=x.device,
                                 dtype=torch.bfloat16)
                 _T.im2col_nhwc16(x, m, int(Hin), int(Win), int(KH), int(KW), int(stride),
                                  int(pad), e)
                 return e
             return to_nhwc16(x, m)
-        a16 = src16(x0, m0, C0)
-        b16 = src16(x1, m1, C1) if src1 is not None else None
+        a16 = src16(x0, m0, C0, plan.expand0)
+        b16 = src16(x1, m1, C1, plan.expand1) if src1 is not None else None
         wt16 = conv_weight_nhwc16(w, C0, C1)
-        y16 = None
-        if out16 and CONV_OUT16 and _NHWC_MEMO is not None:
-            y16 = torch.empty(N, Ho, Wo, Cout, device=x0.device, dtype=torch.bfloat16)
 
         def launch():
             _T.conv_gen_fwd_nhwc16(a16, b16, wt16, int(Cout), int(KH), int(KW), bias, ratio,
@@ -1403,24 +1417,11 @@ def conv_gen(src0, w, *, src1=None, Hin=None, Win=None, stride=1, pad=0, bias=No
             launch.out, launch.stats, launch.y16 = out, stats, y16
             return launch
         launch()
-        if y16 is not None:
-            _NHWC_MEMO[(out.data_ptr(), tuple(out.shape), out._version, 0, -1)] = (y16, out, None)
-        return out, stats
-    if Cout == 1:
-        nb = int(_lib.lib.ainp_conv_gen_workspace(N, Cin, KH, KW, Cout, ch or Ho, cw or Wo))
     else:
-        nb = int(_lib.lib.ainp_conv_gen_workspace(N, Cin, KH, KW, Cout, Ho, Wo))
-        wt = conv_weight_kmajor(w, C0, C1)
-    if nb:
-        ws = torch.empty(-(-nb // 4), device=x0.device)
-    y16 = None
-    if (out16 and bf16 and CONV_OUT16 and OUT16_DIRECT and _NHWC_MEMO is not None
-            and Cout % 8 == 0 and _direct_route(C0, C1, H0, W0, Hin, Win, KH, KW, Cout, want_stats)):
-        # the few-input-channel kernel writes the next conv's channel-last source
-        y16 = torch.empty(N, Ho, Wo, Cout, device=x0.device, dtype=torch.bfloat16)
-    _T.conv_gen_fwd(x0, m0, x1, m1, w, wt, bias, ratio, scale, out, stats, int(Hin), int(Win),
-                    int(stride), int(pad), int(act), float(slope), int(ch), int(cw),
-                    CONV_BF16 if bf16 else 0, ws, y16)
+        wt = conv_weight_kmajor(w, C0, C1) if Cout > 1 else None
+        _T.conv_gen_fwd(x0, m0, x1, m1, w, wt, bias, ratio, scale, out, stats, int(Hin), int(Win),
+                        int(stride), int(pad), int(act), float(slope), int(ch), int(cw),
+                        CONV_BF16 if bf16 else 0, ws, y16)
     if y16 is not None:
         _NHWC_MEMO[(out.data_ptr(), tuple(out.shape), out._version, 0, -1)] = (y16, out, None)
     return out, stats

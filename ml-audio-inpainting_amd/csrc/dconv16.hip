@@ -20,6 +20,7 @@
 //                NHWC run per pixel), 1/sigma applied in the epilogue.
 // The fp32 path (im2col + x6 GEMM + col2im in gan.hip) stays the fp32 one.
 #include "common.h"
+#include "conv_gen_route.h"
 
 namespace ainp {
 namespace d16 {
@@ -33,7 +34,7 @@ __device__ __forceinline__ uint16_t to_bf16(float v) {
 
 // k-values a source of C channels x KK taps occupies in a weight row (tiles of 32)
 __host__ __device__ inline int seg32(int C, int KK) {
-  return (C & 31) ? (KK * C + 31) / 32 * 32 : KK * C;
+  return nhwc16_seg(C, KK);
 }
 
 // sum_z g[z] (* leaky') -> gA [C][ldA] (zero past N*P), gT [N*P][C]

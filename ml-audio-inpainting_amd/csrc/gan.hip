@@ -18,7 +18,10 @@
 // mask and address arithmetic are per tile, not per element ("fast" path).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
+#include "conv_gen_route.h"
 
 namespace ainp {
 
@@ -154,8 +157,6 @@ __device__ __forceinline__ void epilogue_y16_lds(const ConvGenParams& p,
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
 }
-
-constexpr int CG_BK = 32;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 // v_mfma_f32_32x32x2_f32: lane l holds A[row l&31][k l>>5], B[k l>>5][col l&31];
@@ -687,7 +688,6 @@ __global__ __launch_bounds__(256) void conv_gen_splitk_epilogue(ConvGenParams p,
 // bit-identical.  The BatchNorm partials are per (64-pixel block, channel);
 // Y16: the bf16 channel-last copy of act(y) from an LDS transpose of the tile,
 // replacing the nchw_to_nhwc16 pass after the split layers.
-constexpr int SKT_P = 64, SKT_C = 64;
 template <bool Y16>
 __global__ __launch_bounds__(256) void conv_gen_splitk_tile_epilogue(ConvGenParams p, int nsplit,
                                                                      int act) {
@@ -790,28 +790,15 @@ __global__ __launch_bounds__(256) void conv_gen_splitk_tile_epilogue(ConvGenPara
   }
 }
 
-static bool splitk_tile() {
-  static const bool on = [] {
-    const char* e = getenv("AINP_SPLITK_TILE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-static int splitk_epilogue_launch(const ConvGenParams& p, int64_t NP, int nsplit, int act,
+static int splitk_epilogue_launch(const ConvGenParams& p, const ConvGenRoute& r, int act,
                                   hipStream_t s) {
-  if (!splitk_tile()) {
-    hipLaunchKernelGGL(conv_gen_splitk_epilogue, dim3((unsigned)cdiv(NP, 256), p.Cout), dim3(256),
-                       0, s, p, nsplit, act);
-  } else if (p.y16) {
-    hipLaunchKernelGGL(conv_gen_splitk_tile_epilogue<true>,
-                       dim3((unsigned)cdiv(NP, SKT_P), (unsigned)cdiv(p.Cout, SKT_C)), dim3(256), 0,
-                       s, p, nsplit, act);
-  } else {
-    hipLaunchKernelGGL(conv_gen_splitk_tile_epilogue<false>,
-                       dim3((unsigned)cdiv(NP, SKT_P), (unsigned)cdiv(p.Cout, SKT_C)), dim3(256), 0,
-                       s, p, nsplit, act);
-  }
+  const dim3 g((unsigned)r.ex, (unsigned)r.ey);
+  if (r.epilogue == CGP_SPLITK)
+    hipLaunchKernelGGL(conv_gen_splitk_epilogue, g, dim3(256), 0, s, p, r.nsplit, act);
+  else if (r.y16 == CGY_TILE_EPILOGUE)
+    hipLaunchKernelGGL(conv_gen_splitk_tile_epilogue<true>, g, dim3(256), 0, s, p, r.nsplit, act);
+  else
+    hipLaunchKernelGGL(conv_gen_splitk_tile_epilogue<false>, g, dim3(256), 0, s, p, r.nsplit, act);
   return check_launch("conv_gen_splitk_epilogue");
 }
 
@@ -822,8 +809,6 @@ static int splitk_epilogue_launch(const ConvGenParams& p, int64_t NP, int nsplit
 // adds the chunk partials in fixed order, applies 1/sigma, the partial-conv
 // ratio, bias and activation, and writes the (optionally cropped, networks.py:334)
 // output.
-constexpr int C1_CC = 32;
-
 __global__ __launch_bounds__(256) void conv_cout1_partial_kernel(ConvGenParams p, int Hc, int Wc,
                                                                  float* partial) {
   __shared__ float sw[C1_CC * 64];
@@ -1648,8 +1633,6 @@ __global__ void channel_sum_kernel(const float* m, int64_t N, int C, int64_t HW,
 // channel's plane with lane-consecutive pixels.  bf16 (AINP_CONV_BF16): the
 // input value and the weights are rounded to bf16 first, so every product is
 // the exact bf16 x bf16 product the MFMA would form (fp32 accumulation).
-constexpr int SC_K = 160, SC_CO = 64;   // 40 KB of weights in LDS
-
 template <bool B16, bool L16>
 __global__ __launch_bounds__(256) void conv_gen_smallcin_kernel(ConvGenParams p, int act) {
   __shared__ __attribute__((aligned(16))) float sw[SC_K][SC_CO];   // [k][co]
@@ -1787,11 +1770,6 @@ struct Src16 {
   const uint16_t* x;   // [N][Hs][Ws][C] bf16 (mask applied), or [N*Ho*Wo][seg] if exp
   int C, Hs, Ws, up, exp;
 };
-
-// k-values one source contributes to the nhwc16 weight rows
-__host__ __device__ inline int nhwc16_seg(int C, int KK) {
-  return (C & 31) ? (KK * C + 31) / 32 * 32 : KK * C;
-}
 
 template <int BM, bool EXP>
 __global__ __launch_bounds__(256, 4) void conv_gen_nhwc16_kernel(ConvGenParams p, Src16 s0,
@@ -2511,7 +2489,6 @@ __global__ __launch_bounds__(256) void im2col_nhwc16_kernel(
 // coalesced loads, a per-k LDS offset table replaces the per-element tap /
 // channel divisions, and each thread writes 16-byte chunks of the [pix][seg]
 // rows (consecutive threads: consecutive chunks, one contiguous run per block).
-constexpr int IMN_P = 64, IMN_LDS = 4096, IMN_SEG = 256;
 __global__ __launch_bounds__(256) void im2col_nhwc16_rows_kernel(
     const float* __restrict__ x, const float* __restrict__ m, int C, int Hs, int Ws, int up,
     int Hin, int Win, int KH, int KW, int stride, int pad, int Ho, int Wo, int seg,
@@ -2594,53 +2571,210 @@ static ConvSrcDev make_src(const float* x, const float* m, int C, int Hs, int Ws
   s.C = C;
   s.Hs = Hs;
   s.Ws = Ws;
-  if (Hs == Hin && Ws == Win) s.up = 0;
-  else if (2 * Hs == Hin && 2 * Ws == Win) s.up = 1;
-  else s.up = 2;
+  s.up = conv_gen_src_up(Hs, Ws, Hin, Win);
   return s;
 }
 
-static int conv_gen_bm(int Cout) { return Cout > 64 ? 128 : 64; }
-
-// K splits for a launch: small tile grids with long K (the U-Net bottleneck,
-// VGG's last blocks) are split so ~768 workgroups run; >= 8 K tiles per split.
-// For Cout > 64 count the workgroups of the bf16 wide-tile kernel (256 x 128 /
-// 128 x 256 tiles, two per CU) and split grids under 384 of them to ~512: the
-// U-Net decoder's 240-tile layers ran on half the CUs' slots (C4 9.34-9.37 ->
-// 9.24-9.25, C5 11.98-12.00 -> 11.78-11.80 ms/step, profiles/r04t_summary.txt).
-// AINP_CONV_SPLIT_WIDE=0: the old-tile count for every Cout; =3: ~768.
-static int conv_gen_nsplit(int64_t NP, int Cout, int K) {
-  if (Cout == 1) return 1;
-  const int BM = conv_gen_bm(Cout);
-  const int64_t blocks = cdiv(NP, 16384 / BM) * cdiv(Cout, BM);
-  const int nkt = (int)cdiv(K, CG_BK);
-  static const int wide_target = [] {
-    const char* e = getenv("AINP_CONV_SPLIT_WIDE");
-    return (e && e[0] == '0') ? 0 : (e && e[0] == '3') ? 768 : 512;
-  }();
-  if (wide_target && Cout > 64) {
-    const int64_t bw = Cout > 128 ? cdiv(NP, 128) * cdiv(Cout, 256) : cdiv(NP, 256) * cdiv(Cout, 128);
-    if (bw >= 384 || nkt < 16) return 1;
-    int64_t sw = wide_target / bw;
-    if (sw > nkt / 8) sw = nkt / 8;
-    if (sw < 1) sw = 1;
-    const int per = (int)cdiv(nkt, sw);
-    return (int)cdiv(nkt, per);
-  }
-  if (blocks >= 384 || nkt < 16) return 1;
-  int64_t s = cdiv(768, blocks);
-  if (s > nkt / 8) s = nkt / 8;
-  if (s < 1) s = 1;
-  const int per = (int)cdiv(nkt, s);
-  return (int)cdiv(nkt, per);   // no empty split
-}
-
+// ---- the generic convolution: csrc/conv_gen_route.h decides, this launches
 extern "C" int ainp_conv_gen_stat_parts(int64_t N, int Cin, int KH, int KW, int Cout, int64_t Ho,
                                         int64_t Wo) {
-  const int64_t NP = N * Ho * Wo;
-  if (conv_gen_nsplit(NP, Cout, Cin * KH * KW) > 1)
-    return (int)cdiv(NP, splitk_tile() ? SKT_P : 256);
-  return (int)cdiv(NP, 16384 / conv_gen_bm(Cout));
+  const int64_t rows = query_conv_gen(conv_gen_env(), N, Cin, KH, KW, Cout, Ho, Wo, true).stat_rows;
+  return rows > INT_MAX ? INT_MAX : (int)rows;
+}
+
+extern "C" size_t ainp_conv_gen_workspace(int64_t N, int Cin, int KH, int KW, int Cout,
+                                          int64_t Ho, int64_t Wo) {
+  return (size_t)query_conv_gen(conv_gen_env(), N, Cin, KH, KW, Cout, Ho, Wo, false).workspace;
+}
+
+extern "C" int ainp_conv_gen_plan(const AinpConvGenCall* call, AinpConvGenPlan* plan) {
+  if (!call || !plan || call->N < 1 || call->C0 < 1 || call->C1 < 0 || call->Cout < 1 ||
+      call->Hin < 1 || call->Win < 1 || call->KH < 1 || call->KW < 1 || call->stride < 1 ||
+      call->pad < 0 || call->nhwc16_small < 0 || call->nhwc16_small > 2)
+    return record_msg("ainp_conv_gen_plan: bad argument");
+  const ConvGenCall c = conv_gen_call(*call);
+  if (c.Ho < 1 || c.Wo < 1) return record_msg("ainp_conv_gen_plan: empty output");
+  const ConvGenRoute r = route_conv_gen(conv_gen_env(), conv_gen_policy(*call), c);
+  plan->entry = r.entry;
+  plan->expand0 = r.expand0;
+  plan->expand1 = r.expand1;
+  plan->nsplit = r.nsplit;
+  plan->y16_ok = r.y16 != CGY_NOBODY;
+  plan->stat_rows = r.stat_rows;
+  plan->workspace = (size_t)r.workspace;
+  plan->kernel = conv_gen_kernel_id(r.kernel);
+  plan->name = conv_gen_kernel_name(r);
+  plan->refusal = r.ok() ? nullptr : conv_gen_refusal_text(r.refuse);
+  return 0;
+}
+
+extern "C" int ainp_nhwc16_seg(int C, int KK) { return nhwc16_seg(C, KK); }
+
+// What both entry points hand the kernels (source / weight pointers are the
+// entry's own) and the routing call that describes it.
+static ConvGenParams conv_gen_params(int C0, int H0, int W0, int C1, int H1, int W1,
+                                     const float* bias, const float* ratio, const float* scale,
+                                     float* y, double* stats, uint16_t* y16, int64_t N, int Cout,
+                                     int Hin, int Win, int KH, int KW, int stride, int pad,
+                                     float slope) {
+  ConvGenParams p;
+  p.s0 = make_src(nullptr, nullptr, C0, H0, W0, Hin, Win);
+  p.s1 = make_src(nullptr, nullptr, C1, C1 ? H1 : Hin, C1 ? W1 : Win, Hin, Win);
+  p.w = nullptr;
+  p.bias = bias;
+  p.ratio = ratio;
+  p.scale = scale;
+  p.y = y;
+  p.stats = stats;
+  p.partial = nullptr;
+  p.y16 = y16;
+  p.ktiles_per_split = 1 << 30;
+  p.N = (int)N;
+  p.Cin = C0 + C1;
+  p.Cout = Cout;
+  p.Hin = Hin;
+  p.Win = Win;
+  p.Ho = (int)conv_gen_out(Hin, KH, stride, pad);
+  p.Wo = (int)conv_gen_out(Win, KW, stride, pad);
+  p.KH = KH;
+  p.KW = KW;
+  p.stride = stride;
+  p.pad = pad;
+  p.slope = slope;
+  return p;
+}
+
+static ConvGenCall conv_gen_call(const ConvGenParams& p, int64_t N, bool b16, int crop_h,
+                                 int crop_w) {
+  ConvGenCall c;
+  c.N = N;
+  c.C0 = p.s0.C;
+  c.C1 = p.s1.C;
+  c.up0 = p.s0.up;
+  c.up1 = p.s1.up;
+  c.Hin = p.Hin;
+  c.Win = p.Win;
+  c.Ho = p.Ho;
+  c.Wo = p.Wo;
+  c.KH = p.KH;
+  c.KW = p.KW;
+  c.Cout = p.Cout;
+  c.crop_h = crop_h;
+  c.crop_w = crop_w;
+  c.b16 = b16;
+  c.stats = p.stats != nullptr;
+  c.y16 = p.y16 != nullptr;
+  return c;
+}
+
+// a runtime value as a template argument
+template <int A, int B, class F>
+static void pick(int v, F&& f) {
+  if (v == A) f(std::integral_constant<int, A>{});
+  else f(std::integral_constant<int, B>{});
+}
+template <class F>
+static void pick(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// Launches the route's kernel and epilogue.  wt: k-major fp32 weights (NCHW
+// entry, Cout > 1); a / b / wt16: the channel-last entry's operands.
+static int conv_gen_launch(ConvGenParams p, const ConvGenRoute& r, const float* wt, const Src16& a,
+                           const Src16& b, const uint16_t* wt16, int act, int crop_h, int crop_w,
+                           void* workspace, void* stream) {
+  const bool n16 = r.entry == CGE_NHWC16, cout1 = r.epilogue == CGP_COUT1_FINISH;
+  if (cout1 && !workspace) return record_msg(conv_gen_refusal_text(CGR_COUT1));
+  if ((r.kernel == CGK_X6 || r.kernel == CGK_EXACT) && !wt)
+    return record_msg("ainp_conv_gen_fwd: k-major weights (ainp_conv_weight_kmajor) required");
+  if (r.workspace && !workspace)
+    return record_msg(n16 ? "ainp_conv_gen_fwd_nhwc16: split-K needs ainp_conv_gen_workspace"
+                          : "ainp_conv_gen_fwd: split-K needs ainp_conv_gen_workspace");
+  float* part = reinterpret_cast<float*>(workspace);
+  if (r.nsplit > 1) p.partial = part;
+  p.ktiles_per_split = r.ktiles_per_split;
+  hipStream_t s = as_stream(stream);
+  const dim3 grid((unsigned)r.gx, (unsigned)r.gy, (unsigned)r.gz);
+  const int Hc = crop_h > 0 ? crop_h : p.Ho, Wc = crop_w > 0 ? crop_w : p.Wo;
+  const int tco = (int)r.tco, tpx = (int)r.tpx;
+#define AINP_CG(kernel, threads, ...) \
+  hipLaunchKernelGGL((kernel), grid, dim3(threads), 0, s, p, __VA_ARGS__)
+  switch (r.kernel) {
+    case CGK_COUT1_LOOP:
+      AINP_CG(conv_cout1_partial_kernel, 256, Hc, Wc, part);
+      break;
+    case CGK_COUT1_TAPS:
+      if (r.kt == 3) AINP_CG((conv_cout1_partial_b_kernel<3, 4>), 256, Hc, Wc, part);
+      else AINP_CG((conv_cout1_partial_b_kernel<4, 4>), 256, Hc, Wc, part);
+      break;
+    case CGK_SMALLCIN:
+      pick(r.lds16, [&](auto l16) {
+        if (r.b16) AINP_CG((conv_gen_smallcin_kernel<true, decltype(l16)::value>), 256, act);
+        else AINP_CG((conv_gen_smallcin_kernel<false, decltype(l16)::value>), 256, act);
+      });
+      break;
+    case CGK_X6:
+      pick<128, 64>(r.bm, [&](auto bm) {
+        constexpr int BM = decltype(bm)::value;
+        if (r.planes == 3 && r.bk == 16) AINP_CG((conv_gen_x6_kernel<BM, 16, 3>), 256, wt, act);
+        else if (r.planes == 3) AINP_CG((conv_gen_x6_kernel<BM, 32, 3>), 256, wt, act);
+        else if (r.bk == 64) AINP_CG((conv_gen_x6_kernel<BM, 64, 1>), 256, wt, act);
+        else if (r.bk == 16) AINP_CG((conv_gen_x6_kernel<BM, 16, 1>), 256, wt, act);
+        else AINP_CG((conv_gen_x6_kernel<BM, 32, 1>), 256, wt, act);
+      });
+      break;
+    case CGK_EXACT:
+      pick<128, 64>(r.bm, [&](auto bm) {
+        AINP_CG(conv_gen_fwd_kernel<decltype(bm)::value>, 256, wt, act);
+      });
+      break;
+    case CGK_NHWC16_TILES:
+      pick<128, 64>(r.bm, [&](auto bm) {
+        pick(r.expand, [&](auto ex) {
+          AINP_CG((conv_gen_nhwc16_kernel<decltype(bm)::value, decltype(ex)::value>), 256, a, b,
+                  wt16, act);
+        });
+      });
+      break;
+    case CGK_NHWC16_RING:
+      pick<128, 64>(r.bm, [&](auto bm) {
+        pick(r.expand, [&](auto ex) {
+          AINP_CG((conv_gen_nhwc16_ring_kernel<decltype(bm)::value, decltype(ex)::value>), 256, a,
+                  b, wt16, act);
+        });
+      });
+      break;
+    case CGK_NHWC16_WIDE:
+#define AINP_CGW(BM, NW, ...) \
+  AINP_CG((conv_gen_nhwc16_wide_kernel<BM, NW, __VA_ARGS__>), NW * 64, a, b, wt16, act, tco, tpx)
+      pick(r.expand, [&](auto ex) {
+        constexpr bool EX = decltype(ex)::value;
+        if (r.nw == 8)
+          pick<256, 128>(r.bm, [&](auto bm) {
+            pick(r.pf, [&](auto pf) { AINP_CGW(decltype(bm)::value, 8, EX, decltype(pf)::value); });
+          });
+        else if (r.bm == 256) AINP_CGW(256, 4, EX);
+        else if (r.bm == 128) AINP_CGW(128, 4, EX);
+        else AINP_CGW(64, 4, EX);
+      });
+#undef AINP_CGW
+      break;
+    default:
+      return record_msg("ainp_conv_gen_fwd: no kernel");
+  }
+#undef AINP_CG
+  int rc = check_launch(cout1 ? "conv_cout1" : r.kernel == CGK_SMALLCIN ? "conv_gen_smallcin"
+                        : n16 ? "conv_gen_nhwc16" : "conv_gen_fwd");
+  if (rc || r.epilogue == CGP_NONE) return rc;
+  if (cout1) {
+    hipLaunchKernelGGL(conv_cout1_finish_kernel, dim3((unsigned)r.ex), dim3(256), 0, s, p, act, Hc,
+                       Wc, (int)r.gy, part);
+    return check_launch("conv_cout1");
+  }
+  rc = splitk_epilogue_launch(p, r, act, s);
+  if (rc || r.y16 != CGY_TRANSPOSE) return rc;
+  return ainp_nchw_to_nhwc16(p.y, nullptr, p.N, p.Cout, p.Ho, p.Wo, p.y16, stream);
 }
 
 extern "C" int ainp_conv_weight_kmajor(const float* w, int Cout, int C0, int C1, int KH, int KW,
@@ -2651,14 +2785,6 @@ extern "C" int ainp_conv_weight_kmajor(const float* w, int Cout, int C0, int C1,
   hipLaunchKernelGGL(conv_weight_kmajor_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0,
                      as_stream(stream), w, Cout, C0, C1, KH * KW, wt);
   return check_launch("conv_weight_kmajor");
-}
-
-extern "C" size_t ainp_conv_gen_workspace(int64_t N, int Cin, int KH, int KW, int Cout,
-                                          int64_t Ho, int64_t Wo) {
-  if (Cout == 1) return (size_t)cdiv(Cin, C1_CC) * N * Ho * Wo * sizeof(float);
-  const int64_t NP = N * Ho * Wo;
-  const int ns = conv_gen_nsplit(NP, Cout, Cin * KH * KW);
-  return ns > 1 ? (size_t)ns * Cout * NP * sizeof(float) : 0;
 }
 
 extern "C" int ainp_conv_gen_fwd(const float* x0, const float* m0, int C0, int H0, int W0,
@@ -2698,148 +2824,23 @@ extern "C" int ainp_conv_gen_fwd_out16(const float* x0, const float* m0, int C0,
       Hin < 1 || Win < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0 || act < 0 || act > 3 ||
       (flags & ~AINP_CONV_BF16) || (y16 && (Cout % 8 || ((uintptr_t)y16 & 15))))
     return record_msg("ainp_conv_gen_fwd: bad argument (y16: Cout % 8 == 0, 16-byte aligned)");
-  const bool b16 = (flags & AINP_CONV_BF16) != 0;
-  const int Ho = (Hin + 2 * pad - KH) / stride + 1;
-  const int Wo = (Win + 2 * pad - KW) / stride + 1;
-  if (Ho < 1 || Wo < 1) return record_msg("ainp_conv_gen_fwd: empty output");
-  ConvGenParams p;
-  p.s0 = make_src(x0, m0, C0, H0, W0, Hin, Win);
-  p.s1 = make_src(x1, m1, C1, C1 ? H1 : Hin, C1 ? W1 : Win, Hin, Win);
-  if ((p.s0.up == 1 && (H0 * 2 != Hin)) || H0 < 1 || W0 < 1)
-    return record_msg("ainp_conv_gen_fwd: bad source size");
+  ConvGenParams p = conv_gen_params(C0, H0, W0, C1, H1, W1, bias, ratio, scale, y, stats, y16, N,
+                                    Cout, Hin, Win, KH, KW, stride, pad, slope);
+  if (p.Ho < 1 || p.Wo < 1) return record_msg("ainp_conv_gen_fwd: empty output");
+  if (H0 < 1 || W0 < 1) return record_msg("ainp_conv_gen_fwd: bad source size");
+  p.s0.x = x0;
+  p.s0.m = m0;
+  p.s1.x = x1;
+  p.s1.m = m1;
   p.w = w;
-  p.bias = bias;
-  p.ratio = ratio;
-  p.scale = scale;
-  p.y = y;
-  p.stats = stats;
-  p.partial = nullptr;
-  p.y16 = nullptr;
-  p.ktiles_per_split = 1 << 30;
-  p.N = (int)N;
-  p.Cin = C0 + C1;
-  p.Cout = Cout;
-  p.Hin = Hin;
-  p.Win = Win;
-  p.Ho = Ho;
-  p.Wo = Wo;
-  p.KH = KH;
-  p.KW = KW;
-  p.stride = stride;
-  p.pad = pad;
-  p.slope = slope;
-  hipStream_t s = as_stream(stream);
-  if (Cout == 1) {
-    const int Hc = crop_h > 0 ? crop_h : Ho, Wc = crop_w > 0 ? crop_w : Wo;
-    if (stats || Hc > Ho || Wc > Wo || !workspace || KH * KW > 64)
-      return record_msg("ainp_conv_gen_fwd: Cout=1 options (workspace, kernel <= 8x8)");
-    const int64_t np = N * (int64_t)Hc * Wc;
-    const int nchunk = (int)cdiv(p.Cin, C1_CC);
-    float* part = reinterpret_cast<float*>(workspace);
-    // one plain source, whole 32-channel chunks, square 3 / 4 kernels: the
-    // batched-tap variant (AINP_COUT1_B=0: the loop kernel, A/B)
-    static const bool c1b = [] {
-      const char* e = getenv("AINP_COUT1_B");
-      return !(e && e[0] == '0');
-    }();
-    const bool plain = p.s1.C == 0 && p.s0.up == 0 && p.Cin % C1_CC == 0 && KH == KW &&
-                       (int64_t)N * p.Cin * p.s0.Hs * p.s0.Ws * 4 < ((int64_t)1 << 31);
-    if (c1b && plain && KH == 3)
-      hipLaunchKernelGGL((conv_cout1_partial_b_kernel<3, 4>), dim3((unsigned)cdiv(np, 256), nchunk),
-                         dim3(256), 0, s, p, Hc, Wc, part);
-    else if (c1b && plain && KH == 4)
-      hipLaunchKernelGGL((conv_cout1_partial_b_kernel<4, 4>), dim3((unsigned)cdiv(np, 256), nchunk),
-                         dim3(256), 0, s, p, Hc, Wc, part);
-    else
-      hipLaunchKernelGGL(conv_cout1_partial_kernel, dim3((unsigned)cdiv(np, 256), nchunk),
-                         dim3(256), 0, s, p, Hc, Wc, part);
-    hipLaunchKernelGGL(conv_cout1_finish_kernel, dim3((unsigned)cdiv(np, 256)), dim3(256), 0, s, p,
-                       act, Hc, Wc, nchunk, part);
-    return check_launch("conv_cout1");
-  }
-  if (crop_h > 0 || crop_w > 0) return record_msg("ainp_conv_gen_fwd: crop needs Cout=1");
-  // few input channels, one plain source, no BN statistics: the direct kernel
-  static const bool small_ok = [] {
-    const char* e = getenv("AINP_CONV_SMALLCIN");
-    return !(e && e[0] == '0');
-  }();
-  if (small_ok && C1 == 0 && p.s0.up == 0 && !stats && Cout <= SC_CO &&
-      (int64_t)C0 * KH * KW <= SC_K && C0 <= 4) {
-    const int64_t NPs = N * (int64_t)Ho * Wo;
-    p.y16 = y16;
-    // AINP_SMALLCIN_LDS16=0: each thread stores its own pixel's bf16 row (A/B)
-    static const bool l16 = [] {
-      const char* e = getenv("AINP_SMALLCIN_LDS16");
-      return !(e && e[0] == '0');
-    }();
-    const dim3 g((unsigned)cdiv(NPs, 256));
-    if (b16 && l16 && y16 && Cout % 8 == 0)
-      hipLaunchKernelGGL((conv_gen_smallcin_kernel<true, true>), g, dim3(256), 0, s, p, act);
-    else if (b16)
-      hipLaunchKernelGGL((conv_gen_smallcin_kernel<true, false>), g, dim3(256), 0, s, p, act);
-    else if (l16 && y16 && Cout % 8 == 0)
-      hipLaunchKernelGGL((conv_gen_smallcin_kernel<false, true>), g, dim3(256), 0, s, p, act);
-    else
-      hipLaunchKernelGGL((conv_gen_smallcin_kernel<false, false>), g, dim3(256), 0, s, p, act);
-    return check_launch("conv_gen_smallcin");
-  }
-  if (y16) return record_msg("ainp_conv_gen_fwd: y16 is written by the few-input-channel kernel only");
-  if (!wt) return record_msg("ainp_conv_gen_fwd: k-major weights (ainp_conv_weight_kmajor) required");
-  const int BM = conv_gen_bm(Cout);
-  const int64_t NP = N * (int64_t)Ho * Wo;
-  const int K = p.Cin * KH * KW;
-  const int nsplit = conv_gen_nsplit(NP, Cout, K);
-  if (nsplit > 1) {
-    if (!workspace) return record_msg("ainp_conv_gen_fwd: split-K needs ainp_conv_gen_workspace");
-    p.partial = reinterpret_cast<float*>(workspace);
-    p.ktiles_per_split = (int)cdiv(cdiv(K, CG_BK), nsplit);
-  }
-  const int64_t tiles = cdiv(NP, 16384 / BM);
-  dim3 grid((unsigned)tiles, (unsigned)cdiv(Cout, BM), (unsigned)nsplit);
-  // fp32-accurate split-bf16 main loop unless AINP_CONV_EXACT=1 (exact f32 MFMA)
-  static const bool exact = [] {
-    const char* e = getenv("AINP_CONV_EXACT");
-    return e && e[0] == '1';
-  }();
-  static const int xbk = [] {
-    const char* e = getenv("AINP_CONV_GEN_BK");
-    return (e && e[0] == '3') ? 32 : 16;
-  }();
-  // bf16 operands: one plane, 32-deep K-tiles (measured: 64-deep tiles at
-  // 184-212 VGPRs ran the C4 step's convs 1.6x slower); AINP_CONV_GEN_B16_BK
-  // = 16 / 64 selects the other depths
-  static const int b16bk = [] {
-    const char* e = getenv("AINP_CONV_GEN_B16_BK");
-    return (e && e[0] == '6') ? 64 : (e && e[0] == '1') ? 16 : 32;
-  }();
-  const int bk = !b16 ? 0 : (b16bk == 64 && nsplit > 1 && p.ktiles_per_split % 2) ? 32 : b16bk;
-  if (bk == 64 && BM == 128)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<128, 64, 1>), grid, dim3(256), 0, s, p, wt, act);
-  else if (bk == 64)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<64, 64, 1>), grid, dim3(256), 0, s, p, wt, act);
-  else if (bk == 16 && BM == 128)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<128, 16, 1>), grid, dim3(256), 0, s, p, wt, act);
-  else if (bk == 16)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<64, 16, 1>), grid, dim3(256), 0, s, p, wt, act);
-  else if (b16 && BM == 128)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<128, 32, 1>), grid, dim3(256), 0, s, p, wt, act);
-  else if (b16)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<64, 32, 1>), grid, dim3(256), 0, s, p, wt, act);
-  else if (!exact && BM == 128 && xbk == 16)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<128, 16, 3>), grid, dim3(256), 0, s, p, wt, act);
-  else if (!exact && xbk == 16)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<64, 16, 3>), grid, dim3(256), 0, s, p, wt, act);
-  else if (!exact && BM == 128)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<128, 32, 3>), grid, dim3(256), 0, s, p, wt, act);
-  else if (!exact)
-    hipLaunchKernelGGL((conv_gen_x6_kernel<64, 32, 3>), grid, dim3(256), 0, s, p, wt, act);
-  else if (BM == 128)
-    hipLaunchKernelGGL(conv_gen_fwd_kernel<128>, grid, dim3(256), 0, s, p, wt, act);
-  else
-    hipLaunchKernelGGL(conv_gen_fwd_kernel<64>, grid, dim3(256), 0, s, p, wt, act);
-  int rc = check_launch("conv_gen_fwd");
-  if (rc || nsplit == 1) return rc;
-  return splitk_epilogue_launch(p, NP, nsplit, act, s);
+  const ConvGenRoute r =
+      route_conv_gen(conv_gen_env(), conv_gen_policy_nchw(),
+                     conv_gen_call(p, N, (flags & AINP_CONV_BF16) != 0, crop_h, crop_w));
+  if (!r.ok()) return record_msg(conv_gen_refusal_text(r.refuse));
+  // the bf16 copy belongs to the other entry point's routes, but for one
+  if (y16 && r.y16 == CGY_NOBODY) return record_msg(conv_gen_refusal_text(CGR_Y16));
+  return conv_gen_launch(p, r, wt, Src16{}, Src16{}, nullptr, act, crop_h, crop_w, workspace,
+                         stream);
 }
 
 extern "C" int ainp_nchw_to_nhwc16(const float* x, const float* m, int64_t N, int C, int H, int W,
@@ -2886,15 +2887,11 @@ extern "C" int ainp_im2col_nhwc16(const float* x, const float* m, int64_t N, int
   if (sd.up == 1 && Hs * 2 != Hin) return record_msg("ainp_im2col_nhwc16: bad source size");
   const int seg = nhwc16_seg(C, KH * KW);
   const int64_t NP = N * (int64_t)Ho * Wo;
-  // row-staged kernel where its LDS holds the patch (AINP_IM2COL_NHWC16_ROWS=0:
-  // the per-chunk kernel)
-  static const bool rows_env = [] {
-    const char* e = getenv("AINP_IM2COL_NHWC16_ROWS");
-    return !(e && e[0] == '0');
-  }();
+  // row-staged kernel where its LDS holds the patch (ConvGenEnv::im2col_rows
+  // off: the per-chunk kernel)
   const int PWmax = (IMN_P - 1) * stride + KW;
-  if (rows_env && (int64_t)C * KH * PWmax <= IMN_LDS && seg <= IMN_SEG && N <= 65535 &&
-      Ho <= 65535) {
+  if (conv_gen_env().im2col_rows && (int64_t)C * KH * PWmax <= IMN_LDS && seg <= IMN_SEG &&
+      N <= 65535 && Ho <= 65535) {
     hipLaunchKernelGGL(im2col_nhwc16_rows_kernel,
                        dim3((unsigned)cdiv(Wo, IMN_P), (unsigned)Ho, (unsigned)N), dim3(256), 0,
                        as_stream(stream), x, m, C, Hs, Ws, sd.up, Hin, Win, KH, KW, stride, pad,
@@ -2918,24 +2915,12 @@ extern "C" int ainp_conv_weight_nhwc16(const float* w, int Cout, int C0, int C1,
   return check_launch("conv_weight_nhwc16");
 }
 
-// conv_gen_nhwc16 main loop: 0 register-staged, 1 LDS-DMA ring, 2 wide-tile
-// ring of 4 waves, 3 (default) wide-tile ring of 8 waves for Cout > 64 and the
-// register-staged kernel below (tools/conv16_lab.py, profiles/r03_c16b_*: the
-// C4 step's 30 launches 3.98 -> 3.59 ms, all bit-identical).  Initial value
-// from AINP_CONV16 (or AINP_CONV16_RING=1).
-static int g_conv16_variant = -1;
-static int conv16_variant() {
-  if (g_conv16_variant < 0) {
-    const char* e = getenv("AINP_CONV16");
-    const char* r = getenv("AINP_CONV16_RING");
-    g_conv16_variant = (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : ((r && r[0] == '1') ? 1 : 3);
-  }
-  return g_conv16_variant;
-}
-
+// The main loop of the channel-last conv (ConvGenEnv::conv16_variant;
+// tools/conv16_lab.py, profiles/r03_c16b_*: the C4 step's 30 launches 3.98 ->
+// 3.59 ms, all bit-identical), switched in-process.
 extern "C" int ainp_conv16_set_variant(int v) {
-  const int prev = conv16_variant();
-  if (v >= 0 && v <= 3) g_conv16_variant = v;
+  const int prev = conv_gen_env().conv16_variant;
+  if (v >= 0 && v <= 3) conv_gen_env().conv16_variant = v;
   return prev;
 }
 
@@ -2951,118 +2936,17 @@ extern "C" int ainp_conv_gen_fwd_nhwc16_ex(const uint16_t* x0, int C0, int H0, i
       (C0 % 32 == 0 && ((uintptr_t)x0 & 15)) || (C1 % 32 == 0 && ((uintptr_t)x1 & 15)) ||
       ((uintptr_t)wt16 & 15))
     return record_msg("ainp_conv_gen_fwd_nhwc16: bad argument (Cout > 1, 16-B aligned)");
-  const int Ho = (Hin + 2 * pad - KH) / stride + 1;
-  const int Wo = (Win + 2 * pad - KW) / stride + 1;
-  if (Ho < 1 || Wo < 1) return record_msg("ainp_conv_gen_fwd_nhwc16: empty output");
-  Src16 a{x0, C0, H0, W0, 0, C0 % 32 != 0}, b{x1, C1, C1 ? H1 : Hin, C1 ? W1 : Win, 0, C1 % 32 != 0};
-  const ConvSrcDev sa = make_src(nullptr, nullptr, C0, H0, W0, Hin, Win);
-  const ConvSrcDev sb = make_src(nullptr, nullptr, C1, b.Hs, b.Ws, Hin, Win);
-  a.up = sa.up;
-  b.up = sb.up;
-  if (a.up == 1 && H0 * 2 != Hin) return record_msg("ainp_conv_gen_fwd_nhwc16: bad source size");
-  ConvGenParams p;
-  p.s0 = sa;
-  p.s1 = sb;
-  p.w = nullptr;
-  p.bias = bias;
-  p.ratio = ratio;
-  p.scale = scale;
-  p.y = y;
-  p.stats = stats;
-  p.partial = nullptr;
-  p.y16 = y16;
-  p.ktiles_per_split = 1 << 30;
-  p.N = (int)N;
-  p.Cin = C0 + C1;
-  p.Cout = Cout;
-  p.Hin = Hin;
-  p.Win = Win;
-  p.Ho = Ho;
-  p.Wo = Wo;
-  p.KH = KH;
-  p.KW = KW;
-  p.stride = stride;
-  p.pad = pad;
-  p.slope = slope;
-  const int BM = conv_gen_bm(Cout);
-  const int64_t NP = N * (int64_t)Ho * Wo;
-  // the split count follows the unpadded K (ainp_conv_gen_workspace /
-  // _stat_parts); the padded tiles are spread over those splits
-  const int nsplit = conv_gen_nsplit(NP, Cout, p.Cin * KH * KW);
-  const int Kp = nhwc16_seg(C0, KH * KW) + nhwc16_seg(C1, KH * KW);
-  if (nsplit > 1) {
-    if (!workspace) return record_msg("ainp_conv_gen_fwd_nhwc16: split-K needs ainp_conv_gen_workspace");
-    p.partial = reinterpret_cast<float*>(workspace);
-    p.ktiles_per_split = (int)cdiv(Kp / CG_BK, nsplit);
-  }
-  hipStream_t s = as_stream(stream);
-  const dim3 grid((unsigned)cdiv(NP, 16384 / BM), (unsigned)cdiv(Cout, BM), (unsigned)nsplit);
-  const bool exp = a.exp || b.exp;
-  const int variant = conv16_variant();
-  // AINP_CONV16_SMALLCO=2: Cout <= 64 on the 4-wave 64 x 256 wide ring under
-  // the default variant too (A/B)
-  static const bool small_wide = [] {
-    const char* e = getenv("AINP_CONV16_SMALLCO");
-    return e && e[0] == '2';
-  }();
-  if (variant == 2 || (variant == 3 && (Cout > 64 || small_wide))) {
-    const int BW = Cout > 128 ? 256 : (Cout > 64 ? 128 : 64);
-    const int BNW = BW == 256 ? 128 : 256;       // both NW: 256x128 / 128x256 / 64x256
-    const int tco = (int)cdiv(Cout, BW), tpx = (int)cdiv(NP, BNW);
-    const dim3 gw((unsigned)(tco * tpx), (unsigned)nsplit);
-#define AINP_CGW(BMV, NWV, EXPV)                                                                 \
-  hipLaunchKernelGGL((conv_gen_nhwc16_wide_kernel<BMV, NWV, EXPV>), gw, dim3(NWV * 64), 0, s, p, a, \
-                     b, wt16, act, tco, tpx)
-    static const bool wide_pf = [] {
-      const char* e = getenv("AINP_WIDE_PF");
-      return !(e && e[0] == '0');
-    }();
-#define AINP_CGW8(BMV, EXPV)                                                                      \
-  do {                                                                                           \
-    if (wide_pf)                                                                                 \
-      hipLaunchKernelGGL((conv_gen_nhwc16_wide_kernel<BMV, 8, EXPV, true>), gw, dim3(512), 0, s, p, \
-                         a, b, wt16, act, tco, tpx);                                             \
-    else                                                                                         \
-      hipLaunchKernelGGL((conv_gen_nhwc16_wide_kernel<BMV, 8, EXPV, false>), gw, dim3(512), 0, s,  \
-                         p, a, b, wt16, act, tco, tpx);                                          \
-  } while (0)
-    if (variant == 3 && BW > 64) {
-      if (BW == 256) { if (exp) AINP_CGW8(256, true); else AINP_CGW8(256, false); }
-      else { if (exp) AINP_CGW8(128, true); else AINP_CGW8(128, false); }
-#undef AINP_CGW8
-    } else if (BW == 256) { if (exp) AINP_CGW(256, 4, true); else AINP_CGW(256, 4, false); }
-    else if (BW == 128) { if (exp) AINP_CGW(128, 4, true); else AINP_CGW(128, 4, false); }
-    else { if (exp) AINP_CGW(64, 4, true); else AINP_CGW(64, 4, false); }
-#undef AINP_CGW
-  } else if (variant == 1) {
-    if (BM == 128 && exp)
-      hipLaunchKernelGGL((conv_gen_nhwc16_ring_kernel<128, true>), grid, dim3(256), 0, s, p, a, b,
-                         wt16, act);
-    else if (BM == 128)
-      hipLaunchKernelGGL((conv_gen_nhwc16_ring_kernel<128, false>), grid, dim3(256), 0, s, p, a,
-                         b, wt16, act);
-    else if (exp)
-      hipLaunchKernelGGL((conv_gen_nhwc16_ring_kernel<64, true>), grid, dim3(256), 0, s, p, a, b,
-                         wt16, act);
-    else
-      hipLaunchKernelGGL((conv_gen_nhwc16_ring_kernel<64, false>), grid, dim3(256), 0, s, p, a, b,
-                         wt16, act);
-  } else if (BM == 128 && exp)
-    hipLaunchKernelGGL((conv_gen_nhwc16_kernel<128, true>), grid, dim3(256), 0, s, p, a, b, wt16, act);
-  else if (BM == 128)
-    hipLaunchKernelGGL((conv_gen_nhwc16_kernel<128, false>), grid, dim3(256), 0, s, p, a, b, wt16, act);
-  else if (exp)
-    hipLaunchKernelGGL((conv_gen_nhwc16_kernel<64, true>), grid, dim3(256), 0, s, p, a, b, wt16, act);
-  else
-    hipLaunchKernelGGL((conv_gen_nhwc16_kernel<64, false>), grid, dim3(256), 0, s, p, a, b, wt16, act);
-  int rc = check_launch("conv_gen_nhwc16");
-  if (rc || nsplit == 1) return rc;
-  rc = splitk_epilogue_launch(p, NP, nsplit, act, s);
-  if (rc || !y16 || splitk_tile()) return rc;
-  // split-K layers are small: their bf16 copy by the coalesced transpose kernel
-  // (the per-channel epilogue blocks would store it 2 bytes at a time)
-  return ainp_nchw_to_nhwc16(y, nullptr, N, Cout, Ho, Wo, y16, stream);
+  const ConvGenParams p = conv_gen_params(C0, H0, W0, C1, H1, W1, bias, ratio, scale, y, stats,
+                                          y16, N, Cout, Hin, Win, KH, KW, stride, pad, slope);
+  if (p.Ho < 1 || p.Wo < 1) return record_msg("ainp_conv_gen_fwd_nhwc16: empty output");
+  const ConvGenRoute r = route_conv_gen(conv_gen_env(), conv_gen_policy_nhwc16(),
+                                        conv_gen_call(p, N, true, 0, 0));
+  if (!r.ok()) return record_msg(conv_gen_refusal_text(r.refuse));
+  const Src16 a{x0, C0, p.s0.Hs, p.s0.Ws, p.s0.up, r.expand0};
+  const Src16 b{x1, C1, p.s1.Hs, p.s1.Ws, p.s1.up, r.expand1};
+  return conv_gen_launch(p, r, nullptr, a, b, wt16, act, 0, 0, workspace, stream);
 }
+
 
 extern "C" int ainp_conv_gen_fwd_nhwc16(const uint16_t* x0, int C0, int H0, int W0,
                                         const uint16_t* x1, int C1, int H1, int W1,
@@ -3093,11 +2977,8 @@ extern "C" int ainp_pconv_mask(const float* m0, int C0, int H0, int W0, const fl
 #define AINP_PCM(KT)                                                                          \
   hipLaunchKernelGGL(pconv_mask_kernel<KT>, grid, dim3(256), 0, st, s0, s1, (int)N, Hin, Win, KH, \
                      KW, stride, pad, Ho, Wo, winsize, ratio, newmask)
-  static const bool unroll = [] {   // AINP_PCONV_MASK_UNROLL=0: the loop kernel (A/B)
-    const char* e = getenv("AINP_PCONV_MASK_UNROLL");
-    return !(e && e[0] == '0');
-  }();
-  const int kt = unroll && KH == KW ? KH : 0;
+  // ConvGenEnv::pconv_mask_unroll off: the loop kernel (A/B)
+  const int kt = conv_gen_env().pconv_mask_unroll && KH == KW ? KH : 0;
   if (kt == 3) AINP_PCM(3);
   else if (kt == 4) AINP_PCM(4);
   else if (kt == 5) AINP_PCM(5);

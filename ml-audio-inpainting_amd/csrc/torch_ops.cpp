@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ainp.h"
+#include "conv_gen_route.h"   // nhwc16_seg
 
 namespace {
 
@@ -780,16 +781,19 @@ void conv_gen_fwd(const Tensor& x0, const OptT& m0, const OptT& x1, const OptT& 
   if (Cout == 1 && crop_h > 0) numel_is(y, N * crop_h * crop_w, "y");
   else numel_is(y, N * Cout * Ho * Wo, "y");
   const float* pwt = opt(wt, "wt");
-  TORCH_CHECK(Cout == 1 || pwt, "conv_gen: Cout > 1 needs the k-major weights wt");
   double* st = opt<double>(stats, "stats", at::kDouble);
-  if (st)
-    numel_is(*stats,
-             (int64_t)ainp_conv_gen_stat_parts(N, (int)(C0 + C1), (int)KH, (int)KW, (int)Cout, Ho, Wo) *
-                 2 * Cout,
-             "stats");
-  const size_t need = ainp_conv_gen_workspace(N, (int)(C0 + C1), (int)KH, (int)KW, (int)Cout,
-                                              (Cout == 1 && crop_h > 0) ? crop_h : Ho,
-                                              (Cout == 1 && crop_w > 0) ? crop_w : Wo);
+  const bool has_y16 = y16.has_value() && y16->defined();
+  // this entry point's route (csrc/conv_gen_route.h): its statistic rows and
+  // workspace; a call the plan cannot describe is left to the entry point's
+  // own argument check
+  const AinpConvGenCall call = {N, (int)C0, (int)H0, (int)W0, (int)C1, (int)H1, (int)W1, (int)Cout,
+                                (int)Hin, (int)Win, (int)KH, (int)KW, (int)stride, (int)pad,
+                                (int)crop_h, (int)crop_w, (int)flags, st != nullptr, has_y16,
+                                /*nhwc16*/ 0, 0, /*out16*/ 1, 1};
+  AinpConvGenPlan plan = {};
+  ainp_conv_gen_plan(&call, &plan);
+  if (st) numel_is(*stats, plan.stat_rows * 2 * Cout, "stats");
+  const size_t need = plan.workspace;
   void* ws = nullptr;
   if (workspace.has_value() && workspace->defined()) {
     ws = dev<void>(*workspace, "workspace", workspace->scalar_type());
@@ -798,7 +802,7 @@ void conv_gen_fwd(const Tensor& x0, const OptT& m0, const OptT& x1, const OptT& 
     TORCH_CHECK(need == 0, "conv_gen needs a workspace of ", need, " bytes");
   }
   uint16_t* o16 = nullptr;
-  if (y16.has_value() && y16->defined()) {
+  if (has_y16) {
     numel_is(*y16, N * Cout * Ho * Wo, "y16");
     o16 = bf16p(*y16, "y16", true);
   }
@@ -1338,8 +1342,8 @@ void cast_bf16_t(const Tensor& x, const OptT& out, const OptT& outT) {
       "cast_bf16_t");
 }
 
-// k-values one source contributes to an nhwc16 weight row (gan.hip nhwc16_seg)
-int64_t nhwc16_seg(int64_t C, int64_t KK) { return (C % 32) ? (KK * C + 31) / 32 * 32 : KK * C; }
+// k-values one source contributes to an nhwc16 weight row
+int64_t nhwc16_seg(int64_t C, int64_t KK) { return ainp::nhwc16_seg((int)C, (int)KK); }
 
 void nchw_to_nhwc16(const Tensor& x, const OptT& m, const Tensor& out) {
   GUARD(x);

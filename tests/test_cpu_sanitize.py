@@ -13,7 +13,10 @@ libainp_torch_ubsan.so; test_gpu_sanitize.py runs it on the GPU box.
 
   csrc/conv_route.h (which 3x3 conv kernel serves which call, and every
   host-only query derived from it): tests/sanitize/conv_route_check.cpp walks
-  the routing table, the accepted extremes included, as a stand-alone program."""
+  the routing table, the accepted extremes included, as a stand-alone program.
+
+  csrc/conv_gen_route.h (the same for the GAN's general convolution):
+  tests/sanitize/conv_gen_route_check.cpp, likewise."""
 import glob
 import os
 import subprocess
@@ -91,3 +94,20 @@ def test_conv_route_table_under_asan_ubsan(sanitize_build):
     assert model["bf16", "16->32"]["fwd"] == model["bf16", "32->64"]["fwd"] == "fwd_b16dma"
     assert model["bf16", "32->64"]["dgrad"] == "dgrad_b16dma"
     assert model["bf16", "32->64"]["wgrad"] == "wgrad_b16dma"
+
+
+def test_conv_gen_route_table_under_asan_ubsan(sanitize_build):
+    """Every cell of the general convolution's routing table refuses with a
+    known message or names a kernel whose grids are positive and within the
+    launch limits, whose K splits cover every K tile with none empty, whose
+    workspace holds the split-K partial sums and whose statistic rows are its
+    pixel tiles; the oversized shape saturates instead of overflowing."""
+    exe = os.path.join(os.path.dirname(sanitize_build), "conv_gen_route_check")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    env.pop("LD_PRELOAD", None)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-3000:]
+    assert "conv_gen_route_check OK" in out
+    assert "runtime error" not in out and "AddressSanitizer" not in out, out[-3000:]

@@ -276,7 +276,8 @@ def test_conv_gen_direct_kernel_nhwc16_copy(case):
     x = torch.randn(N, C, H, W, generator=g).cuda()
     w = (torch.randn(Cout, C, k, k, generator=g) * 0.2).cuda()
     b = torch.randn(Cout, generator=g).cuda()
-    assert ops._direct_route(C, 0, H, W, H, W, k, k, Cout, False)
+    assert ops.conv_gen_plan(N, C, H, W, 0, 0, 0, Cout, H, W, k, k, s, p,
+                             bf16=True).kernel == "smallcin"
     with ops.nhwc16_memo():
         y, _ = ops.conv_gen((x, None), w, stride=s, pad=p, bias=b, act=act, bf16=True, out16=True)
         key = (y.data_ptr(), tuple(y.shape), y._version, 0, -1)
