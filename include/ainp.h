@@ -378,6 +378,22 @@ int ainp_gemm_bf16nt(int64_t M, int64_t N, int64_t K, const uint16_t* A, int64_t
                      const float* bias_a1, const float* bias_a2, const float* bias_b1,
                      const float* bias_b2, int64_t bias_nsplit, int nsplit, int64_t kc,
                      int64_t strideC, void* stream);
+/* Host-only queries (csrc/gemm_route.h; nothing is launched).
+ * ainp_gemm_bf16nt_tile: the tile ainp_gemm_bf16nt takes for (M, N, K, nsplit)
+ * under this process's environment (AINP_GEMM16_256, AINP_G256_BK64).
+ * ainp_gemm_splitk_granule: what a split-K chunk kc must be a multiple of in a
+ * GEMM family -- G16: ainp_gemm_bf16nt, ainp_wgrad16_nhwc (64); G256:
+ * ainp_gemm_bf16nt_multi (64 where K % 64 == 0, so the 64-deep kernel stays
+ * eligible, else 32); X6: ainp_gemm_x6nt_256, ainp_gemm_x6_multi (16).  0 for
+ * an unknown family. */
+#define AINP_GEMM_TILE_G16 0        /* 128 x 128, g16::gemm_bf16nt_kernel */
+#define AINP_GEMM_TILE_G256 1       /* 256 x 256, 32-deep K-tiles */
+#define AINP_GEMM_TILE_G256_BK64 2  /* 256 x 256, 64-deep K-tiles */
+#define AINP_GEMM_FAMILY_G16 0
+#define AINP_GEMM_FAMILY_G256 1
+#define AINP_GEMM_FAMILY_X6 2
+int ainp_gemm_bf16nt_tile(int64_t M, int64_t N, int64_t K, int nsplit);
+int ainp_gemm_splitk_granule(int family, int64_t K);
 /* Up to 3 bf16-operand GEMMs in ONE launch on the 256 x 256 LDS-DMA tile
  * (csrc/gemm16.hip gemm_bf16nt_256_multi_kernel): the bf16 configuration's
  * layer-0 LSTM backward pair dW_cat = dg^T X beside dX = dg W_cat

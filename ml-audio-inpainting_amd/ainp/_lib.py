@@ -62,6 +62,8 @@ _SIGS = {
                               c_int64, PP, c_int64, c_int64, c_int64, c_float, PP,
                               c_int64, c_int64, c_int64, PP, PP, c_int, c_int64, c_int, P]),
     "ainp_gemm_f32_workspace": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int64, c_int]),
+    "ainp_gemm_bf16nt_tile": (c_int, [c_int64, c_int64, c_int64, c_int]),
+    "ainp_gemm_splitk_granule": (c_int, [c_int, c_int64]),
     "ainp_gemm_f32_ws": (c_int, [c_int64, c_int64, c_int64, c_float, PP, c_int64, c_int64,
                                  c_int64, PP, c_int64, c_int64, c_int64, c_float, PP,
                                  c_int64, c_int64, c_int64, PP, PP, c_int, c_int64, c_int,

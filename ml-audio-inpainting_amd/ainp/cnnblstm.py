@@ -484,15 +484,10 @@ class _BLSTMFn(torch.autograd.Function):
             gwi = None
             dxi = None
             if pair or pair16:
+                # the deferred decoder / projection weight gradients run beside
+                # the pair; joining both side streams first was slower at C2
+                # 
                 dxi = torch.empty(NT, Il, device=dh.device)
-                if ops.PAIR_JOIN:
-                    # (A/B switch, off by default) the work queued on BOTH side
-                    # streams -- the BLSTM's weight gradients and the deferred
-                    # decoder / projection ones -- finishes first at full width:
-                    # the pair kernel (160 KB of LDS per workgroup) cannot share a
-                    # CU with them.  Off, the deferred jobs run beside the pair
-                    # (C2 faster that way)
-                    _join_side(dh.device)
                 if pair:
                     gwi = [torch.empty(4 * H, Il, device=dh.device) for _ in range(2)]
                     ops.lstm_l0_bwd_x6(dg2, wf, wr, inp, dxi, gwi[0], gwi[1])
@@ -518,15 +513,6 @@ class _BLSTMFn(torch.autograd.Function):
                 pass                                                  # dxi from the pair
             elif l016 is not None:
                 dxi = ops.gemm_bf16nt(dg16, l016[1])                 # dg [NT,8H] x W_cat
-            elif Il >= 1024 and ops.DX_X6_256 and not bf16 and not ops.GEMM_EXACT \
-                    and ops.x6_256_eligible(NT, Il, 8 * H, Il):
-                # layer 0 fp32: dX = dg [NT, 8H] . [W_f; W_r] on the 256 x 256
-                # split-pass tile with the k-contiguous W_cat^T [Il, 8H]
-                wt = torch.empty(Il, 8 * H, device=dh.device)
-                ops.transpose_f32(wf, out=wt[:, :4 * H])
-                ops.transpose_f32(wr, out=wt[:, 4 * H:])
-                dxi = torch.empty(NT, Il, device=dh.device)
-                ops.gemm_x6nt_256(dg2.view(NT, 8 * H), wt, wt[:0], dxi, nsplit=1)
             elif Il >= 1024:
                 dxi = torch.empty(NT, Il, device=dh.device)
                 ops.gemm(NT, Il, 4 * H, [dg2, dg2[:, 4 * H:]], 8 * H, 1, [wf, wr], Il, 1,
@@ -550,6 +536,7 @@ class _BLSTMFn(torch.autograd.Function):
             inp, h, gates, cell = saved[4 * l:4 * l + 4]
             wf, hf, bif, bhf, wr, hr, bir, bhr = params[8 * l:8 * l + 8]
             l016 = ctx.l016 if l == 0 else None
+            dg16 = dgT16 = None     # the bf16 layer-0 operands (l016 only)
             Il = inp.shape[1] if l016 is None else ctx.I
             if l == L - 1 and DEFER_EARLY:
                 pre = torch.cuda.Event()      # the decoder backward is done here
@@ -598,12 +585,9 @@ class _BLSTMFn(torch.autograd.Function):
                 # stream's weight-gradient launches, whose host-side issue
                 # would otherwise leave the current stream idle
                 dxi, gwi_of[l] = main_dx(l, dg2, inp, Il, wf, wr, l016, pair, to_sink,
-                                         dg16 if l016 is not None else None,
-                                         dgT16 if l016 is not None else None, pair16)
+                                         dg16, dgT16, pair16)
             def side_work(l=l, dg=dg, dg2=dg2, hp=hp, inp=inp, Il=Il, l016=l016, pair=pair,
-                          pair16=pair16, early=early, to_sink=to_sink,
-                          dg16=dg16 if l016 is not None else None,
-                          dgT16=dgT16 if l016 is not None else None):
+                          pair16=pair16, early=early, to_sink=to_sink, dg16=dg16, dgT16=dgT16):
                 """Layer l's weight / bias gradients on the side stream (and
                 its slots in grads; gwi_of[l] holds the pair's dW_ih)."""
                 with torch.cuda.stream(side):
@@ -655,8 +639,7 @@ class _BLSTMFn(torch.autograd.Function):
             else:
                 side_work()
                 dxi, gwi_of[l] = main_dx(l, dg2, inp, Il, wf, wr, l016, pair, to_sink,
-                                         dg16 if l016 is not None else None,
-                                         dgT16 if l016 is not None else None, pair16)
+                                         dg16, dgT16, pair16)
                 if (pair or pair16) and not to_sink:
                     grads[8 * l], grads[8 * l + 4] = gwi_of[l]
             if l > 0 or ctx.needs_input_grad[0]:
@@ -967,7 +950,7 @@ class _ProjFn(torch.autograd.Function):
         bf16 = ctx.bf16
 
         def wgrad(dw, db, g=g, h=h):
-            S = _split_count(N)
+            S = ops.split_count(N)
             per = N // S
             slabs = torch.empty(S, NO, K, device=h.device, dtype=torch.float32)
             ops.gemm(NO, K, T, [g[i * per] for i in range(S)], T, 1,
@@ -1007,7 +990,7 @@ class _ProjFn(torch.autograd.Function):
         dh = torch.empty(N, T, K, device=g.device, dtype=torch.float32)
         dw = torch.empty(NO, K, device=g.device)
         db = torch.empty(NO, device=g.device)
-        if ctx.defer_wgrad and not ops.PROJ_JOINT:
+        if ctx.defer_wgrad:
             ops.proj_bwd_x6(gp, h2, w, dh=dh.view(N * T, K))
 
             def wgrad(dw, db):
@@ -1020,14 +1003,6 @@ class _ProjFn(torch.autograd.Function):
             ops.proj_bwd_x6(gp, h2, w, dh=dh.view(N * T, K), dw=dw)
             ops.rowsum_batched(gp.view(1, NO, N * T), out=db)
         return dh, dw, db, None, None, None, None, None
-
-
-def _split_count(n):
-    """Largest divisor of n that is <= 8 (pointer batches of the GEMM)."""
-    for s in (8, 4, 2, 1):
-        if n % s == 0:
-            return s
-    return 1
 
 
 # ------------------------------------------------------------------ loss

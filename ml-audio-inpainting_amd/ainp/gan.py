@@ -848,13 +848,6 @@ def _d_backward16(ctx, g, inv, ins, outs, us, vs, params):
     return (gx, None, None, None, None, None, *grads)
 
 
-def _split_count(n):
-    for s in (8, 4, 2, 1):
-        if n % s == 0:
-            return s
-    return 1
-
-
 class Discriminator(nn.Module):
     """networks.py:375-409."""
 

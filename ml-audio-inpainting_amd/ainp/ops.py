@@ -250,13 +250,55 @@ def _gemm_workspace(device, stream: int, M, N, K, nptr, nstrided, ksplit):
     return buf
 
 
-def _chunks_for(K, tiles, target_blocks=512, min_rows=64):
-    """Split count S (a divisor of K) so tiles*S ~ target workgroups."""
-    want = max(1, min(K // min_rows, target_blocks // max(1, tiles)))
-    for s in range(want, 0, -1):
-        if K % s == 0:
+def largest_divisor_at_most(n, cap):
+    for s in range(max(1, min(n, cap)), 0, -1):
+        if n % s == 0:
             return s
     return 1
+
+
+def split_count(n):
+    """8, 4, 2 or 1: the largest of them dividing n (pointer batches of a GEMM)."""
+    return next(s for s in (8, 4, 2, 1) if n % s == 0)
+
+
+def _chunks_for(K, tiles, target_blocks=512, min_rows=64):
+    """Split count S (a divisor of K) so tiles*S ~ target workgroups."""
+    return largest_divisor_at_most(K, min(K // min_rows, target_blocks // max(1, tiles)))
+
+
+# ------------------------------------------------------------------ split-K
+# One chunk rule and one slab helper for every split-K GEMM below; the C side
+# validates the same rule once (csrc/gemm_route.h splitk_covers).
+FAMILY_G16, FAMILY_G256, FAMILY_X6 = 0, 1, 2      # include/ainp.h AINP_GEMM_FAMILY_*
+
+
+@functools.lru_cache(maxsize=None)
+def splitk_granule(family, K=0):
+    """What a split-K chunk of a GEMM family must be a multiple of: its K-tile
+    depth (ainp_gemm_splitk_granule; FAMILY_G256 depends on K)."""
+    return int(_lib.lib.ainp_gemm_splitk_granule(family, K))
+
+
+def split_k(K, S, granule):
+    """(S, kc): S chunks of kc, whole granules, covering K with none empty; the
+    one-chunk (1, K) when the rounded chunk does not give S pieces."""
+    if S <= 1 or K <= 0:
+        return 1, K
+    kc = -(-K // S // granule) * granule
+    return (S, kc) if -(-K // kc) == S else (1, K)
+
+
+def _slab_target(out, S):
+    """Where a split-K launch writes: out itself, or S fresh slabs of its shape."""
+    return out if S == 1 else torch.empty(S, *out.shape, device=out.device, dtype=torch.float32)
+
+
+def _slab_sum(C, S, out):
+    """After the launch: the S slabs of C summed in fixed order into out."""
+    if S > 1:
+        sum_slabs(C, S, out=out.view(-1))
+    return out
 
 
 def gemm_tn_splitk(a, lda, b, ldb, K, M, N, offsets_b=(0, 0), bf16=False):
@@ -331,18 +373,22 @@ def cast_bf16_t(x, out=None, outT=None):
 B16_PROJ_SPLIT = int(os.environ.get("AINP_B16_PROJ_SPLIT", "3"))
 
 
-GEMM16_256 = os.environ.get("AINP_GEMM16_256", "1")[:1] != "0"
+def gemm_bf16nt_tile(M, N, K, nsplit=1):
+    """The tile ainp_gemm_bf16nt takes (ainp_gemm_bf16nt_tile, csrc/gemm_route.h):
+    0 the 128 x 128 one, 1 / 2 the 256 x 256 one on 32- / 64-deep K-tiles."""
+    return int(_lib.lib.ainp_gemm_bf16nt_tile(int(M), int(N), int(K), int(nsplit)))
+
+
+# AINP_GEMM16_256 as the library read it (=0: every ainp_gemm_bf16nt on the
+# 128 x 128 tile): whether an unsplit 512 x 512 GEMM goes to the 256 x 256 tile
+GEMM16_256 = gemm_bf16nt_tile(512, 512, 64) != 0
 
 
 def b16_proj_split(M, N, K):
     """Split count the bf16 layer-0 projection [M, N] x K uses (cnnblstm,
     bench): B16_PROJ_SPLIT only where ainp_gemm_bf16nt routes the split GEMM
-    to the 256 x 256 tile (gemm16.hip: M >= 8N, M, N >= 512, at most 1536
-    128 x 128 tiles, K % 32 == 0, AINP_GEMM16_256 on); else unsplit."""
-    tiles128 = -(-M // 128) * -(-N // 128)
-    ok = (GEMM16_256 and M >= 8 * N and M >= 512 and N >= 512 and tiles128 <= 1536
-          and K % 32 == 0)
-    return B16_PROJ_SPLIT if ok else 1
+    to the 256 x 256 tile; else unsplit."""
+    return B16_PROJ_SPLIT if gemm_bf16nt_tile(M, N, K, B16_PROJ_SPLIT) != 0 else 1
 
 
 def gemm_bf16nt(A, B, K=None, out=None, bias=(None, None, None, None), bias_nsplit=0,
@@ -354,28 +400,16 @@ def gemm_bf16nt(A, B, K=None, out=None, bias=(None, None, None, None), bias_nspl
     K = A.shape[1] if K is None else int(K)
     if out is None:
         out = torch.empty(M, N, device=A.device, dtype=torch.float32)
-    S = int(nsplit)
-    kc = -(-K // S // 64) * 64 if S > 1 else K
-    if S > 1 and (-(-K // kc) != S or not out.is_contiguous()):
-        S, kc = 1, K
-    if S == 1:
-        _T.gemm_bf16nt(A, B, out, K, *bias, int(bias_nsplit), 1, K)
-        return out
-    slabs = torch.empty(S, M, N, device=A.device, dtype=torch.float32)
-    _T.gemm_bf16nt(A, B, slabs, K, *bias, int(bias_nsplit), S, kc)
-    sum_slabs(slabs, S, out=out.view(-1))
-    return out
+    S, kc = split_k(K, int(nsplit) if out.is_contiguous() else 1, splitk_granule(FAMILY_G16))
+    C = _slab_target(out, S)
+    _T.gemm_bf16nt(A, B, C, K, *bias, int(bias_nsplit), S, kc)
+    return _slab_sum(C, S, out)
 
 
 # fp32 layer-0 projection on the 256 x 256 LDS-DMA tile (ainp_gemm_x6nt_256):
 # split 3 fills the 256 CUs with the 168 tiles of M = 10688, N = 1024
 # (2.28 -> 2.09 ms, tools/x6_256_lab.cpp); AINP_X6_256=0 keeps ainp_gemm_f32.
 X6_256 = os.environ.get("AINP_X6_256", "1") != "0"
-# layer-0 fp32 data gradient on the same tile (W_ih^T transposed per step).  Off:
-# inside the step it ran 4.11 ms against the 128 x 128 x6 kernel's 3.10 ms, as
-# the side-stream weight-gradient GEMM cannot co-reside with its 144 KB of LDS
-# (profiles/r02_s11_dx_x6_256_ab.txt); AINP_DX_X6_256=1 turns it on.
-DX_X6_256 = os.environ.get("AINP_DX_X6_256", "0") == "1"
 _X6_SPLIT = 3
 
 
@@ -396,17 +430,11 @@ def transpose_f32(x, out=None):
 def gemm_x6nt_256(A, B1, B2, out, bias=(None, None, None, None), bias_nsplit=0, nsplit=None):
     """out [M, N1+N2] = A [M, K] . [B1; B2]^T + bias, fp32 on the three-piece
     bf16 split (ainp_gemm_x6nt_256); split-K slabs summed in fixed order."""
-    M, K = A.shape
-    N = B1.shape[0] + B2.shape[0]
-    S = _X6_SPLIT if nsplit is None else int(nsplit)
-    if S == 1:
-        _T.gemm_x6nt_256(A, B1, B2, out, *bias, int(bias_nsplit), 1, K)
-        return out
-    kc = -(-K // S // 16) * 16
-    slabs = torch.empty(S, M, N, device=A.device, dtype=torch.float32)
-    _T.gemm_x6nt_256(A, B1, B2, slabs, *bias, int(bias_nsplit), S, kc)
-    sum_slabs(slabs, S, out=out.view(-1))
-    return out
+    K = A.shape[1]
+    S, kc = split_k(K, _X6_SPLIT if nsplit is None else int(nsplit), splitk_granule(FAMILY_X6))
+    C = _slab_target(out, S)
+    _T.gemm_x6nt_256(A, B1, B2, C, *bias, int(bias_nsplit), S, kc)
+    return _slab_sum(C, S, out)
 
 
 # bf16 MFMA rate per resident workgroup slot and the HBM rate, for the split-K
@@ -420,14 +448,13 @@ def _splitk_bf16(M, N, K, slots=768, max_split=16):
     """Split count S for a bf16 GEMM over a small M x N: minimise the wave-quantised
     MFMA time ceil(tiles*S/slots) * tile_time(K/S) plus the slab round trip."""
     tiles = -(-M // 128) * -(-N // 128)
+    g = splitk_granule(FAMILY_G16)
     best, best_t = 1, None
     for S in range(1, max_split + 1):
-        kc = -(-K // S // 64) * 64
-        if kc < 64:
-            break
-        Sr = -(-K // kc)
+        Sr, kc = split_k(K, S, g)
         if Sr != S:
             continue
+        kc = -(-kc // g) * g      # whole K-tiles (the unsplit K too)
         t = -(-tiles * S // slots) * 2.0 * 128 * 128 * kc / _B16_TILE_RATE
         if S > 1:
             t += 2.0 * S * M * N * 4 / _SLAB_RATE
@@ -469,8 +496,6 @@ def gemm_x6_multi(problems):
 # AINP_L0_BWD_X6R=0 keeps the layer-0 backward pair on two streams (128 x 128
 # x6 kernels: dX on the current stream, the split-K weight gradient beside it)
 L0_BWD_X6R = os.environ.get("AINP_L0_BWD_X6R", "1") != "0"
-# AINP_PAIR_JOIN=1 (measured slower, 16.6 vs 16.1 ms C2 step, profiles/r03_ab1_*): the pair waits for the side stream's weight gradients
-PAIR_JOIN = os.environ.get("AINP_PAIR_JOIN", "0") == "1"
 # AINP_MAIN_FIRST=0: the BLSTM backward issues each layer's data gradient after
 # the side stream's weight-gradient launches (the round-3 order); default: before
 MAIN_FIRST = os.environ.get("AINP_MAIN_FIRST", "1") != "0"
@@ -513,29 +538,18 @@ def gemm_x6r_nt(A, B1, B2, out, bias=(None, None, None, None), bias_nsplit=0, ns
     M, K = A.shape
     N1 = B1.shape[0]
     N = N1 + B2.shape[0]
-    S = _X6_SPLIT if nsplit is None else int(nsplit)
-    kc = -(-K // S // 16) * 16 if S > 1 else K
-    if S > 1 and -(-K // kc) != S:
-        S, kc = 1, K
-    kw = dict(B2=B2 if B2.shape[0] else None, b_nsplit=N1 if B2.shape[0] else 0,
-              bias=bias, bias_nsplit=bias_nsplit)
-    if S == 1:
-        gemm_x6_multi([x6_problem(A, B1, out, M=M, N=N, K=K, lda=A.stride(0), ldb=B1.stride(0),
-                                  ldc=out.stride(0), **kw)])
-        return out
-    slabs = torch.empty(S, M, N, device=A.device, dtype=torch.float32)
-    gemm_x6_multi([x6_problem(A, B1, slabs, M=M, N=N, K=K, lda=A.stride(0), ldb=B1.stride(0),
-                              ldc=N, nsplit=S, kc=kc, strideC=M * N, **kw)])
-    sum_slabs(slabs, S, out=out.view(-1))
-    return out
+    S, kc = split_k(K, _X6_SPLIT if nsplit is None else int(nsplit), splitk_granule(FAMILY_X6))
+    C = _slab_target(out, S)
+    gemm_x6_multi([x6_problem(A, B1, C, M=M, N=N, K=K, lda=A.stride(0), ldb=B1.stride(0),
+                              ldc=C.stride(-2), B2=B2 if B2.shape[0] else None,
+                              b_nsplit=N1 if B2.shape[0] else 0, bias=bias,
+                              bias_nsplit=bias_nsplit, nsplit=S, kc=kc, strideC=M * N)])
+    return _slab_sum(C, S, out)
 
 
 # AINP_PROJ_X6R=0 keeps the fp32 output-projection backward on gemm_f32
 # (pointer-batched FMA GEMMs over the [N, C*F, T] gradient as it lies)
 PROJ_X6R = os.environ.get("AINP_PROJ_X6R", "1") != "0"
-# AINP_PROJ_JOINT=1: dh and dW in one launch even when the weight gradient
-# could be deferred to the side stream (A/B)
-PROJ_JOINT = os.environ.get("AINP_PROJ_JOINT", "0") == "1"
 _X6R_SLOTS = 256        # one 160 KB-LDS workgroup per CU
 
 
@@ -553,33 +567,34 @@ def _x6r_makespan(items_kt, slots=_X6R_SLOTS):
     return end
 
 
-@functools.lru_cache(maxsize=64)
-def x6r_splits(shapes, max_split=16):
-    """Split-K counts for problems (M, N, K) launched together on the x6r tile:
-    minimise the estimated makespan plus the slab traffic (each split > 1 writes
+def _makespan_splits(shapes, max_split, family, depth, kt_time):
+    """Split-K counts for problems (M, N, K) launched together on a 256 x 256
+    tile, one workgroup per CU: minimise the estimated makespan (K-tiles of
+    `depth`, kt_time seconds each) plus the slab traffic (each split > 1 writes
     S slabs that ainp_sum_slabs reads back).  Returns ((S, kc), ...)."""
     def opts(M, N, K):
-        out = []
-        for S in range(1, max_split + 1):
-            kc = -(-K // S // 16) * 16 if S > 1 else K
-            if S > 1 and -(-K // kc) != S:
-                continue
-            out.append((S, kc))
-        return out
+        chunks = (split_k(K, S, splitk_granule(family, K)) for S in range(1, max_split + 1))
+        return [(S, kc) for S, (Sr, kc) in enumerate(chunks, 1) if Sr == S]
     best, best_t = None, None
     for combo in itertools.product(*(opts(*s) for s in shapes)):
         items = []
         slab = 0.0
         for (M, N, K), (S, kc) in zip(shapes, combo):
             tiles = -(-M // 256) * -(-N // 256)
-            items += [kc // 16] * (tiles * S)
+            items += [kc // depth] * (tiles * S)
             if S > 1:
                 slab += (S + 1) * M * N * 4
-        # K-tile of a 256 x 256 x16 x6 item ~ 4.5 us at the measured rate
-        t = _x6r_makespan(items) * 4.5e-6 + slab / _SLAB_RATE
+        t = _x6r_makespan(items) * kt_time + slab / _SLAB_RATE
         if best_t is None or t < best_t:
             best, best_t = combo, t
     return best
+
+
+@functools.lru_cache(maxsize=64)
+def x6r_splits(shapes, max_split=16):
+    """_makespan_splits on the x6r tile: a 256 x 256 x 16 x6 K-tile ~ 4.5 us at
+    the measured rate."""
+    return _makespan_splits(shapes, max_split, FAMILY_X6, 16, 4.5e-6)
 
 
 def proj_bwd_x6_eligible(NT, NO, K):
@@ -605,20 +620,19 @@ def proj_bwd_x6(gp, h, w, dh=None, dw=None):
     probs, outs = [], []
     if dh is not None:
         (S, kc), = x6r_splits(((NT, K, NO),))
-        C = dh if S == 1 else torch.empty(S, NT, K, device=gp.device)
+        C = _slab_target(dh, S)
         probs.append(x6_problem(gp, w, C, M=NT, N=K, K=NO, lda=NT, ldb=K, ldc=K, a_kmajor=True,
                                 b_kmajor=True, nsplit=S, kc=kc, strideC=NT * K))
-        outs.append((dh, C, S))
+        outs.append((C, S, dh))
     if dw is not None:
         (S, kc), = x6r_splits(((NO, K, NT),))
-        C = dw if S == 1 else torch.empty(S, NO, K, device=gp.device)
+        C = _slab_target(dw, S)
         probs.append(x6_problem(gp, h, C, M=NO, N=K, K=NT, lda=NT, ldb=K, ldc=K, b_kmajor=True,
                                 nsplit=S, kc=kc, strideC=NO * K))
-        outs.append((dw, C, S))
+        outs.append((C, S, dw))
     gemm_x6_multi(probs)
-    for o, C, S in outs:
-        if S > 1:
-            sum_slabs(C, S, out=o.view(-1))
+    for done in outs:
+        _slab_sum(*done)
 
 
 # AINP_B16_PAIR=0: the bf16 layer-0 backward keeps dX (128 x 128 tiles) on the
@@ -634,34 +648,10 @@ B16_KM = os.environ.get("AINP_B16_KM", "1") != "0"
 
 @functools.lru_cache(maxsize=64)
 def g256_splits(shapes, max_split=16):
-    """Split-K counts for bf16 problems (M, N, K) launched together by
-    ainp_gemm_bf16nt_multi (256 x 256 tiles, 32-deep K-tiles, one workgroup per
-    CU): minimise the estimated makespan plus the slab round trip, as
-    x6r_splits does for the x6r tile.  Returns ((S, kc), ...)."""
-    def opts(M, N, K):
-        out = []
-        # 64-deep K-tiles where K allows (gemm16.hip tile256b needs 64 | kc)
-        g = 64 if K % 64 == 0 else 32
-        for S in range(1, max_split + 1):
-            kc = -(-K // S // g) * g if S > 1 else K
-            if S > 1 and -(-K // kc) != S:
-                continue
-            out.append((S, kc))
-        return out
-    best, best_t = None, None
-    for combo in itertools.product(*(opts(*sh) for sh in shapes)):
-        items = []
-        slab = 0.0
-        for (M, N, K), (S, kc) in zip(shapes, combo):
-            tiles = -(-M // 256) * -(-N // 256)
-            items += [kc // 32] * (tiles * S)
-            if S > 1:
-                slab += (S + 1) * M * N * 4
-        # a 256 x 256 x 32 bf16 K-tile ~ 1.1 us at the measured per-CU rate
-        t = _x6r_makespan(items) * 1.1e-6 + slab / _SLAB_RATE
-        if best_t is None or t < best_t:
-            best, best_t = combo, t
-    return best
+    """_makespan_splits for ainp_gemm_bf16nt_multi: a 256 x 256 x 32 bf16 K-tile
+    ~ 1.1 us at the measured per-CU rate; chunks of whole 64-deep K-tiles where
+    K allows (gemm16.hip tile256b needs 64 | kc), else 32-deep."""
+    return _makespan_splits(shapes, max_split, FAMILY_G256, 32, 1.1e-6)
 
 
 def gemm_bf16nt_multi(problems):
@@ -685,11 +675,9 @@ def wgrad_bf16_km(dg16_cols, x16, NT, out):
     split over K by the makespan model, slabs summed in fixed order."""
     rows, I = out.shape
     (S, kc), = g256_splits(((rows, I, NT),))
-    C = out if S == 1 else torch.empty(S, rows, I, device=out.device)
+    C = _slab_target(out, S)
     gemm_bf16nt_multi([(dg16_cols, x16, C, NT, S, kc, True, True)])
-    if S > 1:
-        sum_slabs(C, S, out=out.view(-1))
-    return out
+    return _slab_sum(C, S, out)
 
 
 def l0_bwd_bf16_eligible(NT, I, H):
@@ -709,14 +697,11 @@ def lstm_l0_bwd_bf16(dg16, dgT16, wT16, xB16, dx, gcat, km=False):
     NT, G8 = dg16.shape
     I = xB16.shape[1] if km else xB16.shape[0]
     (Sw, kcw), (Sx, kcx) = g256_splits(((G8, I, NT), (NT, I, G8)))
-    Cw = gcat if Sw == 1 else torch.empty(Sw, G8, I, device=dg16.device)
-    Cx = dx if Sx == 1 else torch.empty(Sx, NT, I, device=dg16.device)
+    Cw, Cx = _slab_target(gcat, Sw), _slab_target(dx, Sx)
     pw = (dg16, xB16, Cw, NT, Sw, kcw, True, True) if km else (dgT16, xB16, Cw, NT, Sw, kcw)
     gemm_bf16nt_multi([pw, (dg16, wT16, Cx, G8, Sx, kcx)])
-    if Sw > 1:
-        sum_slabs(Cw, Sw, out=gcat.view(-1))
-    if Sx > 1:
-        sum_slabs(Cx, Sx, out=dx.view(-1))
+    _slab_sum(Cw, Sw, gcat)
+    _slab_sum(Cx, Sx, dx)
 
 
 def gemm_bf16nt_splitk(A, B, K, out=None, max_split=16):
@@ -727,16 +712,11 @@ def gemm_bf16nt_splitk(A, B, K, out=None, max_split=16):
         out = torch.empty(M, N, device=A.device, dtype=torch.float32)
     if not out.is_contiguous():
         raise ValueError("gemm_bf16nt_splitk: out must be contiguous")
-    S = _splitk_bf16(M, N, K, max_split=max_split)
+    S, kc = split_k(int(K), _splitk_bf16(M, N, K, max_split=max_split), splitk_granule(FAMILY_G16))
     _work("gemm_bf16nt", 2.0 * M * N * K)
-    if S == 1:
-        _T.gemm_bf16nt(A, B, out, int(K), None, None, None, None, 0, 1, int(K))
-        return out
-    kc = -(-K // S // 64) * 64
-    slabs = torch.empty(S, M, N, device=A.device, dtype=torch.float32)
-    _T.gemm_bf16nt(A, B, slabs, int(K), None, None, None, None, 0, S, kc)
-    sum_slabs(slabs, S, out=out.view(-1))
-    return out
+    C = _slab_target(out, S)
+    _T.gemm_bf16nt(A, B, C, int(K), None, None, None, None, 0, S, kc)
+    return _slab_sum(C, S, out)
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None) -> torch.Tensor:
@@ -1597,13 +1577,6 @@ def im2col(x, k, stride, pad, ones_row=False, ldp=None):
     return col
 
 
-def largest_divisor_at_most(n, cap):
-    for s in range(max(1, min(n, cap)), 0, -1):
-        if n % s == 0:
-            return s
-    return 1
-
-
 def gemm_batched_splitk(M, N, Kd, As, sam, sak, Bs, sbk, sbn, out, *, alpha=1.0,
                         per_batch_out=False, target_blocks=768, min_k=256, bf16=False):
     """C = alpha * sum_b A_b B_b (or C_b = alpha * A_b B_b when per_batch_out),
@@ -1714,15 +1687,13 @@ def wgrad16_nhwc(gA, x16, k, stride, pad, max_split=512):
     Cout, ldA = gA.shape[0], gA.shape[1]
     Cin = x16.shape[3]
     Ncol = Cin * k * k + 1
-    S = _splitk_bf16(Cout, Ncol, ldA, max_split=max_split)
-    kc = -(-ldA // S // 64) * 64 if S > 1 else ldA
+    S, kc = split_k(ldA, _splitk_bf16(Cout, Ncol, ldA, max_split=max_split),
+                    splitk_granule(FAMILY_G16))
     G = torch.empty(S, Cout, Ncol, device=gA.device, dtype=torch.float32)
     _T.wgrad16_nhwc(gA, x16, int(k), int(stride), int(pad), G, int(S), int(kc))
     if S == 1:
         return G[0]
-    out = torch.empty(Cout, Ncol, device=gA.device, dtype=torch.float32)
-    sum_slabs(G, S, out=out.view(-1))
-    return out
+    return _slab_sum(G, S, torch.empty(Cout, Ncol, device=gA.device, dtype=torch.float32))
 
 
 def nhwc16_memo_get(x):

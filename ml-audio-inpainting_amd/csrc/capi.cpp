@@ -4,6 +4,7 @@
 #include <stdio.h>
 
 #include "common.h"
+#include "gemm_route.h"
 
 namespace ainp {
 static thread_local char g_last_error[512] = "";
@@ -20,6 +21,16 @@ int record_msg(const char* msg) {
 }  // namespace ainp
 
 extern "C" int ainp_abi_version(void) { return 1; }
+
+// Host-only GEMM queries (gemm_route.h: what the launchers themselves call)
+extern "C" int ainp_gemm_bf16nt_tile(int64_t M, int64_t N, int64_t K, int nsplit) {
+  // a split's chunk is whole g16 K-tiles, so only the unsplit kc (= K) matters
+  return ainp::route_gemm_bf16nt(M, N, K, nsplit, nsplit == 1 ? K : ainp::G16_BK,
+                                 ainp::gemm_env()).tile;
+}
+extern "C" int ainp_gemm_splitk_granule(int family, int64_t K) {
+  return ainp::splitk_granule(family, K);
+}
 
 // Per-phase trace ranges (SURVEY §5 tracing): roctx ranges of the
 // rocprofiler-sdk marker API, recorded by `rocprofv3 --marker-trace`; a no-op

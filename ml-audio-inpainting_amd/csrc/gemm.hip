@@ -25,9 +25,8 @@
 //  x6: K-tile 16; three bf16 planes [row][16 k] per operand with 48-byte rows
 //    (conflict-free ds_read_b128 fragments: lane (r, h) reads k = 8h..8h+7 of
 //    row r, the 32x32x16 operand map, identical for A and B).
-#include <stdlib.h>
-
 #include "common.h"
+#include "gemm_route.h"
 
 namespace ainp {
 
@@ -915,11 +914,7 @@ extern "C" int ainp_gemm_f32_ex(int64_t M, int64_t N, int64_t K, float alpha,
   const unsigned gy = ksplit == 1 ? 1u : (ksplit == 2 ? (unsigned)nptr : (unsigned)nb);
   const dim3 grid((unsigned)(tiles_m * tiles_n), gy);
   float* ws = reinterpret_cast<float*>(workspace);
-  static const bool k64 = [] {
-    const char* e = getenv("AINP_GEMM_B16_KT");
-    return e && e[0] == '6';
-  }();
-  if (pm == PM_B16 && k64)
+  if (pm == PM_B16 && gemm_env().b16_kt64)
     dispatch_gemm<PM_B16K64>(sk, akc, bkc, avec, bvec, grid, s, M, N, K, alpha, p, lda, ldb,
                              beta, scm, scn, nseg, (int)tiles_n, g, ws);
   else if (pm == PM_B16)

@@ -19,15 +19,14 @@
 // blockIdx.y = split s covers k in [s*kc, min(K, (s+1)*kc)) and writes slab
 // C + s*strideC (summed by ainp_sum_slabs in fixed order).  Unsplit GEMMs
 // with M, N >= 512 and at most 1536 tiles of 128 x 128 run on g256 below
-// instead (256 x 256 tiles, LDS-DMA ring; routing rule at the launcher).
+// instead (256 x 256 tiles, LDS-DMA ring; routing rule in gemm_route.h).
 #include "common.h"
-
-#include <stdlib.h>
+#include "gemm_route.h"
 
 namespace ainp {
 namespace g16 {
 
-constexpr int BM = 128, BN = 128, BK = 64, THREADS = 256;
+constexpr int BM = G16_BM, BN = G16_BN, BK = G16_BK, THREADS = 256;
 constexpr int RS = BK * 2 + 16;      // image row bytes: 64 bf16 + 16 B pad
 constexpr int IMG = 128 * RS;        // one operand image
 
@@ -384,7 +383,7 @@ __global__ __launch_bounds__(THREADS, 3) void wgrad16_nhwc_kernel(
 // destination is lane-linear), so the 16 lanes of a ds_read_b128 quarter
 // (16 consecutive rows, one k-chunk) hit 16 distinct 16-byte bank slots.
 namespace g256 {
-constexpr int BM = 256, BN = 256, BK = 32, THREADS = 512, NSTAGE = 4;
+constexpr int BM = 256, BN = 256, BK = G256_BK, THREADS = 512, NSTAGE = 4;
 constexpr int ROWB = BK * 2;             // 64 bytes per image row
 constexpr int IMG = BM * ROWB;           // 16 KB per operand per stage
 constexpr int STAGE = 2 * IMG;           // A + B
@@ -568,7 +567,7 @@ __device__ __forceinline__ void tile256(int64_t M, int64_t N, const uint16_t* __
 // barriers (twice the 32-deep ring's), one K-tile in flight across each
 // barrier, the next k-step's fragments read while the current one's MFMAs run.
 namespace b64 {
-constexpr int BK = 64, NST = 2, ROWB = 2 * BK, IMG = BM * ROWB, STAGE = 2 * IMG;
+constexpr int BK = G256_BK64, NST = 2, ROWB = 2 * BK, IMG = BM * ROWB, STAGE = 2 * IMG;
 static_assert(NST * STAGE == LDS_BYTES, "the 32-deep ring's 128 KB");
 
 __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ (row & 7); }
@@ -839,7 +838,7 @@ using g256::BM;
 using g256::BN;
 using g256::NSTAGE;
 using g256::THREADS;
-constexpr int BK = 16;                   // fp32 k per tile: 64-byte rows
+constexpr int BK = X6_256_BK;            // fp32 k per tile: 64-byte rows
 constexpr int ROWB = BK * 4;
 constexpr int IMG = BM * ROWB;
 constexpr int STAGE = 2 * IMG;
@@ -1150,15 +1149,6 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_x6nt_256s_kernel(
 
 using namespace ainp;
 
-// AINP_G256_BK64=0: the 32-deep 4-stage ring for every g256 GEMM (A/B)
-static bool g256_bk64() {
-  static const bool v = [] {
-    const char* e = getenv("AINP_G256_BK64");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
 extern "C" int ainp_gemm_bf16nt(int64_t M, int64_t N, int64_t K, const uint16_t* A, int64_t lda,
                                 const uint16_t* B, int64_t ldb, float* C, int64_t ldc,
                                 const float* bias_a1, const float* bias_a2, const float* bias_b1,
@@ -1168,30 +1158,14 @@ extern "C" int ainp_gemm_bf16nt(int64_t M, int64_t N, int64_t K, const uint16_t*
       lda % 8 || ldb % 8 || lda < K || ldb < K || ldc < N || (K % 8) ||
       ((uintptr_t)A & 15) || ((uintptr_t)B & 15))
     return record_msg("ainp_gemm_bf16nt: bad argument (16-byte aligned rows, K % 8 == 0)");
-  if (nsplit > 1 && (kc < g16::BK || kc % g16::BK || (int64_t)nsplit * kc < K ||
-                     (int64_t)(nsplit - 1) * kc >= K || strideC < M * ldc))
+  if (!splitk_covers(K, nsplit, kc, g16::BK) || (nsplit > 1 && strideC < M * ldc))
     return record_msg("ainp_gemm_bf16nt: split-K needs kc % 64 == 0 covering K, strideC >= M*ldc");
   if (nsplit == 1) kc = K;
   if (M == 0 || N == 0) return AINP_OK;
   g16::Bias b{bias_a1, bias_a2, bias_b1, bias_b2, bias_nsplit};
-  // large GEMMs on the 256 x 256 LDS-DMA kernel (bit-identical: same MFMA, same
-  // k order); ops._splitk_bf16 applies this rule to its split choice
-  static const bool use256 = [] {  // AINP_GEMM16_256=0 keeps every GEMM on g16 (A/B runs)
-    const char* e = getenv("AINP_GEMM16_256");
-    return !(e && e[0] == '0');
-  }();
-  // Routing: the 256 x 256 tile (one workgroup per CU, 128 KB of LDS) only
-  // for unsplit GEMMs whose 128 x 128 grid is at most two rounds of its 768
-  // resident slots -- the layer-0 projection (672 tiles): 522 -> 482 us inside
-  // the step.  Measured inside the step it loses where another GEMM runs beside
-  // it on the side stream: the data gradient (10836 tiles) 706 -> 891 us, the
-  // split-K weight gradient 621 -> 1325 us (it cannot co-reside with the
-  // 3-workgroups-per-CU kernel next to it).
-  // A split tall-and-narrow GEMM (M >= 8N: the layer-0 projection, 168 tiles
-  // of 256 x 256 -> 504 workgroups at split 3) also runs on g256.
-  const int64_t tiles128 = cdiv(M, g16::BM) * cdiv(N, g16::BN);
-  if (use256 && (nsplit == 1 || M >= 8 * N) && M >= 512 && N >= 512 && tiles128 <= 1536 &&
-      K % g256::BK == 0) {
+  // which tile, and why: gemm_route.h (ops.b16_proj_split asks the same function)
+  const int tile = route_gemm_bf16nt(M, N, K, nsplit, kc, gemm_env()).tile;
+  if (tile != AINP_GEMM_TILE_G16) {
     static const bool lds_ok =
         hipFuncSetAttribute((const void*)g256::gemm_bf16nt_256_kernel,
                             hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1202,7 +1176,7 @@ extern "C" int ainp_gemm_bf16nt(int64_t M, int64_t N, int64_t K, const uint16_t*
     if (!lds_ok) return record_msg("ainp_gemm_bf16nt: cannot reserve 128 KB of LDS");
     const int64_t tn = cdiv(N, g256::BN);
     const dim3 grid((unsigned)(cdiv(M, g256::BM) * tn), (unsigned)nsplit);
-    if (g256_bk64() && K % g256::b64::BK == 0 && kc % g256::b64::BK == 0)
+    if (tile == AINP_GEMM_TILE_G256_BK64)
       hipLaunchKernelGGL(g256::gemm_bf16nt_256b_kernel, grid, dim3(g256::THREADS), g256::LDS_BYTES,
                          as_stream(stream), M, N, K, A, lda, B, ldb, C, ldc, kc, strideC, b,
                          (int)tn);
@@ -1234,8 +1208,7 @@ extern "C" int ainp_gemm_bf16nt_multi(const ainp_bf16_problem* probs, int nprobs
         s.ldb < (s.b_kmajor ? s.N : s.K) || s.ldc < s.N || (s.a_kmajor && s.M % 8) ||
         (s.b_kmajor && s.N % 8) ||
         ((uintptr_t)s.A & 15) || ((uintptr_t)s.B & 15) || nsplit > 65535 ||
-        (nsplit > 1 && (kc < g256::BK || kc % g256::BK || (int64_t)nsplit * kc < s.K ||
-                        (int64_t)(nsplit - 1) * kc >= s.K || s.strideC < s.M * s.ldc)))
+        !splitk_covers(s.K, nsplit, kc, g256::BK) || (nsplit > 1 && s.strideC < s.M * s.ldc))
       return record_msg("ainp_gemm_bf16nt_multi: bad problem (K, kc % 32 == 0 covering K; "
                         "16-byte aligned k-contiguous rows; strideC >= M*ldc when split)");
     g256::MProb& d = job.p[q];
@@ -1251,7 +1224,7 @@ extern "C" int ainp_gemm_bf16nt_multi(const ainp_bf16_problem* probs, int nprobs
     d.first = first;
     first += (d.items + 7) / 8 * 8;
   }
-  job.bk64 = g256_bk64() ? 1 : 0;
+  job.bk64 = gemm_env().g256_bk64 ? 1 : 0;
   for (int q = 0; q < nprobs; ++q)
     if (job.p[q].K % g256::b64::BK || job.p[q].kc % g256::b64::BK) job.bk64 = 0;
   static const bool lds_ok =
@@ -1275,8 +1248,7 @@ extern "C" int ainp_wgrad16_nhwc(const uint16_t* gA, int64_t ldA, int Cout, cons
   const int64_t NP = N * (int64_t)Ho * Wo;
   if (Ho < 1 || Wo < 1 || ldA < NP) return record_msg("ainp_wgrad16_nhwc: bad shape (ldA >= N*Ho*Wo)");
   const int64_t K = ldA;   // gA is zero past N*Ho*Wo, as im2col16's columns
-  if (nsplit > 1 && (kc < g16::BK || kc % g16::BK || (int64_t)nsplit * kc < K ||
-                     (int64_t)(nsplit - 1) * kc >= K))
+  if (!splitk_covers(K, nsplit, kc, g16::BK))
     return record_msg("ainp_wgrad16_nhwc: split-K needs kc % 64 == 0 covering ldA");
   if (nsplit == 1) kc = K;
   const int64_t Ncol = (int64_t)Cin * k * k + 1;
@@ -1297,9 +1269,7 @@ extern "C" int ainp_gemm_x6nt_256(int64_t M, int64_t N, int64_t K, const float* 
                                   const float* bias_a2, const float* bias_b1,
                                   const float* bias_b2, int64_t bias_nsplit, int nsplit,
                                   int64_t kc, int64_t strideC, void* stream) {
-  if (nsplit < 1 || nsplit > 65535 ||
-      (nsplit > 1 && (kc < x6_256::BK || kc % x6_256::BK || (int64_t)nsplit * kc < K ||
-                      (int64_t)(nsplit - 1) * kc >= K || strideC < M * ldc)))
+  if (!splitk_covers(K, nsplit, kc, x6_256::BK) || (nsplit > 1 && strideC < M * ldc))
     return record_msg("ainp_gemm_x6nt_256: split-K needs kc % 16 == 0 covering K, strideC >= M*ldc");
   if (nsplit == 1) kc = K;
   if (M < 0 || N < 0 || K < 0 || !A || !B1 || !C || lda % 4 || ldb % 4 || lda < K || ldb < K ||
@@ -1309,11 +1279,6 @@ extern "C" int ainp_gemm_x6nt_256(int64_t M, int64_t N, int64_t K, const float* 
     return record_msg("ainp_gemm_x6nt_256: bad argument (16-byte aligned k-contiguous rows, "
                       "K % 16 == 0, bsplit % 256 == 0 or bsplit == N)");
   if (M == 0 || N == 0) return AINP_OK;
-  // AINP_X6_SPLITPASS=0 keeps the per-fragment-split kernel (A/B runs)
-  static const bool splitpass = [] {
-    const char* e = getenv("AINP_X6_SPLITPASS");
-    return !(e && e[0] == '0');
-  }();
   static const bool lds_ok =
       hipFuncSetAttribute((const void*)x6_256::gemm_x6nt_256_kernel,
                           hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1325,7 +1290,7 @@ extern "C" int ainp_gemm_x6nt_256(int64_t M, int64_t N, int64_t K, const float* 
   g16::Bias b{bias_a1, bias_a2, bias_b1, bias_b2, bias_nsplit};
   const int64_t tn = cdiv(N, x6_256::BN);
   const dim3 grid((unsigned)(cdiv(M, x6_256::BM) * tn), (unsigned)nsplit);
-  if (splitpass)
+  if (gemm_env().x6_splitpass)
     hipLaunchKernelGGL(x6_256::gemm_x6nt_256s_kernel, grid, dim3(x6_256::THREADS),
                        x6_256::LDS_BYTES_S, as_stream(stream), M, N, K, A, lda, B1, B2, ldb,
                        bsplit, C, ldc, kc, strideC, b, (int)tn);

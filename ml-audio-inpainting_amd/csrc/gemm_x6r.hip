@@ -27,13 +27,12 @@
 // cover the two LSTM directions (B rows n >= b_nsplit, B or A columns
 // k >= *_ksplit from a second tensor; C rows m >= c_msplit to a second one).
 #include "common.h"
-
-#include <stdlib.h>
+#include "gemm_route.h"
 
 namespace ainp {
 namespace x6r {
 
-constexpr int BM = 256, BN = 256, BK = 16, THREADS = 512;
+constexpr int BM = 256, BN = 256, BK = X6R_BK, THREADS = 512;
 constexpr int ROWB = BK * 4;                 // fp32 N image: 64-byte rows
 constexpr int IMG = BM * ROWB;               // 16 KB per operand per stage
 constexpr int STAGE = 2 * IMG;               // A + B
@@ -453,9 +452,8 @@ extern "C" int ainp_gemm_x6_multi(const ainp_x6_problem* probs, int nprobs, void
            (s.b_ksplit > 0 ? (s.b_ksplit % x6r::BK == 0 && s.b_ksplit < K)
                            : (s.b_nsplit > 0 && s.b_nsplit % x6r::BN == 0 && s.b_nsplit < N));
     if (s.C2) ok = ok && s.c_msplit > 0 && s.c_msplit % x6r::BM == 0 && s.c_msplit < M;
-    if (nsplit > 1)
-      ok = ok && kc >= x6r::BK && kc % x6r::BK == 0 && (int64_t)nsplit * kc >= K &&
-           (int64_t)(nsplit - 1) * kc < K && s.strideC >= (s.C2 ? s.c_msplit : M) * s.ldc;
+    ok = ok && splitk_covers(K, nsplit, kc, x6r::BK) &&
+         (nsplit == 1 || s.strideC >= (s.C2 ? s.c_msplit : M) * s.ldc);
     if (s.A2 && nsplit > 1) ok = ok && s.a_ksplit % kc == 0;   // no K-tile straddles
     if (!ok)
       return record_msg("ainp_gemm_x6_multi: bad problem (K % 16, 16-byte aligned operands, "
@@ -470,25 +468,15 @@ extern "C" int ainp_gemm_x6_multi(const ainp_x6_problem* probs, int nprobs, void
     d.tiles_m = (int)cdiv(M, x6r::BM);
     d.tiles_n = (int)cdiv(N, x6r::BN);
     // m-first groups where 8 / tiles_m n-tiles x tiles_m tiles fill a group of
-    // 8 exactly (AINP_X6R_MFAST=0: n-first everywhere, A/B)
-    static const bool mfast_env = [] {
-      const char* e = getenv("AINP_X6R_MFAST");
-      return !(e && e[0] == '0');
-    }();
-    d.mfast = (mfast_env && (d.tiles_m == 2 || d.tiles_m == 4 || d.tiles_m == 8) &&
+    // 8 exactly (GemmEnv::x6r_mfast off: n-first everywhere, A/B)
+    d.mfast = (gemm_env().x6r_mfast && (d.tiles_m == 2 || d.tiles_m == 4 || d.tiles_m == 8) &&
                d.tiles_n >= 8) ? 1 : 0;
     d.items = (int64_t)d.tiles_m * d.tiles_n * nsplit;
     d.first = first;
     first += (d.items + 7) / 8 * 8;
   }
   if (first > 0x7fffffff) return record_msg("ainp_gemm_x6_multi: grid too large");
-  // AINP_X6R_APF=0: A fragments read right before their MFMA group and the
-  // split skipped past the last tile (the round-4 main loop), for A/B
-  static const bool apf = [] {
-    const char* e = getenv("AINP_X6R_APF");
-    return !(e && e[0] == '0');
-  }();
-  if (apf)
+  if (gemm_env().x6r_apf)   // off: the round-4 main loop (A/B)
     hipLaunchKernelGGL(x6r::gemm_x6r_kernel<true>, dim3((unsigned)first), dim3(x6r::THREADS), 0,
                        as_stream(stream), job);
   else

@@ -150,7 +150,8 @@ HOST_ONLY = {"ainp_abi_version", "ainp_build_target", "ainp_last_error", "ainp_r
              "ainp_l1_pow10_loss_slots", "ainp_range_push", "ainp_range_pop", "ainp_mark",
              "ainp_conv16_set_variant", "ainp_conv3x3_dy16_ok", "ainp_conv3x3_io16_ok",
              "ainp_conv3x3_cl_ok", "ainp_conv3x3_dgrad_cfnt_ok",
-             "ainp_conv3x3_dgrad_bnr_nodx_ok", "ainp_conv_gen_plan", "ainp_nhwc16_seg"}
+             "ainp_conv3x3_dgrad_bnr_nodx_ok", "ainp_conv_gen_plan", "ainp_nhwc16_seg",
+             "ainp_gemm_bf16nt_tile", "ainp_gemm_splitk_granule"}
 
 
 def test_torch_library_registers_every_gpu_entry_point():

@@ -16,7 +16,10 @@ libainp_torch_ubsan.so; test_gpu_sanitize.py runs it on the GPU box.
   the routing table, the accepted extremes included, as a stand-alone program.
 
   csrc/conv_gen_route.h (the same for the GAN's general convolution):
-  tests/sanitize/conv_gen_route_check.cpp, likewise."""
+  tests/sanitize/conv_gen_route_check.cpp, likewise.
+
+  csrc/gemm_route.h (the GEMM launchers' split-K cover rule and the tile
+  ainp_gemm_bf16nt takes): tests/sanitize/gemm_route_check.cpp, likewise."""
 import glob
 import os
 import subprocess
@@ -111,3 +114,32 @@ def test_conv_gen_route_table_under_asan_ubsan(sanitize_build):
     assert r.returncode == 0, out[-3000:]
     assert "conv_gen_route_check OK" in out
     assert "runtime error" not in out and "AddressSanitizer" not in out, out[-3000:]
+
+
+def test_gemm_route_under_asan_ubsan(sanitize_build):
+    """splitk_covers equals the launchers' former two-product expression
+    wherever that cannot overflow and refuses cleanly at kc = INT64_MAX,
+    K = INT64_MAX, nsplit = 65535; route_gemm_bf16nt equals the former launcher
+    condition under both AINP_GEMM16_256 settings and names the kernels DESIGN
+    section 4 names for the layer-0 GEMMs."""
+    exe = os.path.join(os.path.dirname(sanitize_build), "gemm_route_check")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    env.pop("LD_PRELOAD", None)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-3000:]
+    assert "gemm_route_check OK" in out
+    assert "runtime error" not in out and "AddressSanitizer" not in out, out[-3000:]
+    # "model gemm16_256=<0|1> g256_bk64=<0|1> proj=<kernel> dx=<kernel> dw=<kernel>"
+    model = {tuple(line.split()[1:3]): dict(kv.split("=") for kv in line.split()[3:])
+             for line in out.splitlines() if line.startswith("model ")}
+    assert len(model) == 4
+    g16 = "g16::gemm_bf16nt_kernel"
+    for key, m in model.items():
+        assert m["dx"] == m["dw"] == g16, key
+    # the split layer-0 projection on the 256 x 256 tile; AINP_GEMM16_256=0: on g16
+    assert model["gemm16_256=1", "g256_bk64=0"]["proj"] == "g256::gemm_bf16nt_256_kernel"
+    assert model["gemm16_256=1", "g256_bk64=1"]["proj"] == "g256::gemm_bf16nt_256b_kernel"
+    assert model["gemm16_256=0", "g256_bk64=0"]["proj"] == g16
+    assert model["gemm16_256=0", "g256_bk64=1"]["proj"] == g16
