@@ -248,6 +248,61 @@ int ainp_ar_extrapolate(double* sol, int64_t n_segments, int64_t stride, const i
 size_t ainp_ar_extrapolate_workspace(int64_t n_segments, int n_max, int p, int gap_max,
                                      int method);
 
+/* Window-wise Janssen inpainting, the janssen_hann / janssen_rect /
+ * janssen_tukey rows of the same comparison (utils/segmentation_inp.m as
+ * train.m:146-172 drives it): two streams around ainp_janssen_ex.  Float64.
+ * The support of a gap is sup_len samples of its signal from the signal index
+ * `origin` (negative, or past the end: those samples read as observed zeros),
+ * zero-padded to the circular length L = S * a.  Window s of S holds the
+ * circular indices (s * a - floor(w / 2) + i) mod L, i = 0 .. w-1.  A window
+ * with some, not all, samples missing is one row of the Janssen batch.
+ *
+ * ainp_janssen_windows cuts the rows: sol[r][i] = signal sample * gana[shape][i],
+ * zero on the row's missing run [gap_start[r], gap_start[r] + gap_len[r]), on
+ * the padding and outside the signal.  signals: `total` float64 samples, every
+ * signal of the batch end to end; sig_off int64 [n_rows]: where the row's
+ * signal starts in it.  row_tab int32 [n_rows][6]: sig_len, origin, sup_len,
+ * L, window index, shape.  gap_start, gap_len int32 [n_rows]: the tables
+ * ainp_janssen_ex then takes (with n[r] = w).  gana [n_shapes][w]: the
+ * analysis windows, made on the host.  Rows of any number of signals, gaps and
+ * shapes go in one launch; a row whose entries contradict one another (L < w,
+ * sup_len > L, window index * a >= L, shape >= n_shapes, a signal outside
+ * [0, total)) is written as zeros.
+ *
+ * ainp_janssen_ola puts the gaps back.  gap_off int64 [n_gaps]: the gap's
+ * first sample in `signals`; gap_tab int32 [n_gaps][6]: h (missing samples),
+ * c0 (support index of the first), L, row0, n_rows (its rows are row0 .. row0
+ * + n_rows - 1, ascending window index), shape.  Per missing sample c = c0 + j:
+ *   value = sum_rows sol[r][i_r] * gsyn[shape][i_r] / rescale,
+ *   i_r = (c - win_r * a + floor(w / 2)) mod L   (rows with i_r < w only),
+ *   rescale = sum_{s < L / a, i_s < w} gana[shape][i_s] * gsyn[shape][i_s],
+ * both sums in ascending window order; rescale counts every window of the
+ * support, also those with all samples missing, which have no row and add
+ * zeros.  The value goes to signals[gap_off + j]; observed samples are never
+ * written.  history (nullable) [n_gaps][maxit][out_stride]: the same from
+ * row_history [n_rows][maxit][hist_stride], the history ainp_janssen_ex wrote
+ * (hist_stride = its row length, the longest gap_len of the batch), for every
+ * iteration; both or neither.  A NaN of row_history (an iteration a window did
+ * not complete, where the caller prefilled with NaN) goes through the sum.
+ * No atomics, fixed order: the same bits on every call.  A gap whose entries
+ * contradict one another or reach outside `signals` is skipped.
+ * Supported: a divides w, w / a >= 2, 2 <= w <= min(stride, 16384), n_shapes
+ * >= 1, total >= 1; ola also 1 <= h_max <= 2048 (the longest h, sizes the
+ * grid) and with history 1 <= maxit <= 1000, out_stride >= h_max.  Anything
+ * else is AINP_EINVAL without a launch.  Neither needs a workspace. */
+int ainp_janssen_windows(const double* signals, int64_t total, const int64_t* sig_off,
+                         const int32_t* row_tab, const int32_t* gap_start,
+                         const int32_t* gap_len, int64_t n_rows, int w, int a,
+                         const double* gana, int n_shapes, double* sol, int64_t stride,
+                         void* stream);
+int ainp_janssen_ola(const double* sol, int64_t n_rows, int64_t stride,
+                     const double* row_history, int maxit, int64_t hist_stride,
+                     const int32_t* row_tab, const int32_t* gap_start, const int32_t* gap_len,
+                     const int64_t* gap_off, const int32_t* gap_tab, int64_t n_gaps, int h_max,
+                     int w, int a, const double* gana, const double* gsyn, int n_shapes,
+                     double* signals, int64_t total, double* history, int64_t out_stride,
+                     void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* fp32 GEMM on MFMA (fp32-accurate bf16 split by default, exact f32 on flag) */
 /* ------------------------------------------------------------------------ */

@@ -260,6 +260,11 @@ _SIGS = {
     "ainp_ar_extrapolate": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, c_int, P, P,
                                     c_size_t, P]),
     "ainp_ar_extrapolate_workspace": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    # window-wise Janssen: the gather and the overlap-add (csrc/janssen_windows.hip)
+    "ainp_janssen_windows": (c_int, [P, c_int64, P, P, P, P, c_int64, c_int, c_int, P, c_int, P,
+                                     c_int64, P]),
+    "ainp_janssen_ola": (c_int, [P, c_int64, c_int64, P, c_int, c_int64, P, P, P, P, P, c_int64,
+                                 c_int, c_int, c_int, P, P, c_int, P, c_int64, P, c_int64, P]),
 }
 
 EXPORTED = tuple(_SIGS)

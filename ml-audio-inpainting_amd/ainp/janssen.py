@@ -8,6 +8,13 @@ the whole batch is one launch of ainp_janssen_ex (csrc/janssen.hip, float64)
 or of ainp_ar_extrapolate (csrc/ar_extrapolate.hip).
 Segments are clipped to the signal (train.m:134-135 indexes past the ends for
 a gap within w of them).  gap_sdr is train.m:196 / model_eval.m:60.
+
+The window-wise rows (utils/segmentation_inp.m on the support train.m:146-172
+cuts with offset.m and min_sig_supp_2.m; Hann, rectangular and Tukey windows)
+are plan_windows / janssen_windowed at the end of the file: every window with
+missing samples, of every gap, signal and window shape, is one row of the same
+ainp_janssen_ex launch, between the gather and the overlap-add of
+csrc/janssen_windows.hip.
 """
 from __future__ import annotations
 
@@ -226,3 +233,228 @@ def gap_sdr(clean, restored, mask):
     den = np.sum((clean[miss] - restored[miss]) ** 2)
     with np.errstate(divide="ignore", invalid="ignore"):
         return float(10.0 * np.log10(num / den))
+
+
+# ------------------------------------------------------------ window-wise
+# utils/segmentation_inp.m as train.m:146-172 drives it (the janssen_hann,
+# janssen_rect and janssen_tukey rows), restated without LTFAT: DESIGN §14.
+WTYPES = ("hann", "rect", "tukey")
+W_MAX = N_MAX
+
+
+def wtype_key(wtype):
+    """segmentation_inp's `wtype` ("hann" | "rect" | "tukey", any case as
+    strcmpi) -> its lower-case name."""
+    key = wtype.lower() if isinstance(wtype, str) else wtype
+    if key not in WTYPES:
+        raise ValueError(f"wtype must be one of {sorted(WTYPES)}, got {wtype!r}")
+    return key
+
+
+def _cdiv(x, y):
+    return -((-x) // y)
+
+
+def gap_support(start, end, w, a):
+    """[lo, hi) (0-based, may leave the signal) that train.m:147-150 hands to
+    segmentation_inp for the gap [start, end): offset(s, f, a, 'half') and
+    min_sig_supp_2(w, a, 0, s, f, N, 1, off) with s = start + 1, f = end."""
+    s, f = start + 1, end
+    c = _cdiv(s + f, 2)
+    off = c - (1 + ((c - 1) // a) * a + _cdiv(a, 2))
+    first = _cdiv(s - _cdiv(w, 2), a) + 1
+    mid = 1 + (first - 1) * a + off % a          # centre of the first window on the gap
+    if mid - a + _cdiv(w, 2) - 1 >= s:
+        mid -= a
+    q = mid - _cdiv(w // 2, a) * a
+    last = mid + ((f + w // 2 - mid) // a) * a
+    Q = last + _cdiv(_cdiv(w, 2), a) * a
+    return q - 1, Q - 1
+
+
+def window_pair(wtype, w, a):
+    """(gana, gsyn) of segmentation_inp.m:74-87, float64 [w].  hann: the
+    periodic Hann and its painless dual for the shift a; rect: ones and that
+    Hann; tukey: MATLAB tukeywin(w) (r = 0.5) for both."""
+    key = wtype_key(wtype)
+    i = np.arange(w, dtype=np.float64)
+    hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * i / w)
+    if key == "rect":
+        return np.ones(w), hann
+    if key == "tukey":
+        t = np.linspace(0.0, 1.0, w)
+        g = np.ones(w)
+        lo, hi = t < 0.25, t >= 0.75
+        g[lo] = 0.5 * (1.0 + np.cos(4.0 * np.pi * (t[lo] - 0.25)))
+        g[hi] = 0.5 * (1.0 + np.cos(4.0 * np.pi * (t[hi] - 0.75)))
+        return g, g.copy()
+    idx = np.arange(w)
+    den = np.zeros(w)
+    for k in range(w // a):
+        den += hann[(idx - k * a) % w] ** 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return hann, hann / den
+
+
+def window_rescale(gana, gsyn, a):
+    """The overlap-add weight sum_k (gana gsyn)[m + k a] per residue m of the
+    window index modulo a (segmentation_inp.m's `rescale`, which repeats with
+    period a on the circular support)."""
+    return (gana * gsyn).reshape(-1, a).sum(axis=0)
+
+
+@dataclass
+class WindowPlan:
+    """The tables of one window-wise call.  Signals lie end to end in one
+    buffer, once per window shape (shape-major).  One row per window that
+    holds some, not all, missing samples; one gap entry per (shape, signal,
+    gap); a gap's rows are consecutive, in ascending window order."""
+    wtypes: tuple
+    w: int
+    a: int
+    total: int
+    gana: np.ndarray          # [n_shapes, w]
+    gsyn: np.ndarray
+    sig_off: np.ndarray       # int64 [n_rows]
+    row_tab: np.ndarray       # int32 [n_rows, 6]: sig_len, origin, sup_len, L, window, shape
+    gap_start: np.ndarray     # int32 [n_rows], relative to the window
+    gap_len: np.ndarray
+    gap_off: np.ndarray       # int64 [n_gaps]
+    gap_tab: np.ndarray       # int32 [n_gaps, 6]: h, c0, L, row0, n_rows, shape
+    gap_signal: np.ndarray    # int32 [n_gaps]
+    gap_range: np.ndarray     # int32 [n_gaps, 2]: [start, end) in the signal
+
+    def __len__(self):
+        return len(self.sig_off)
+
+
+def plan_windows(masks, p=512, w=4096, a=1024, wtypes=("hann",)):
+    """The batch layout of the window-wise algorithm for a list of boolean
+    observed masks and a sequence of window shapes.  ValueError for what is not
+    covered: a not dividing w, w / a < 2, w not in (p, 16384], an overlap-add
+    weight that is not positive, a window that holds a second gap, a run of
+    more than 2048 missing samples."""
+    w, a, p = int(w), int(a), int(p)
+    if a < 1 or w < 1 or w % a:
+        raise ValueError(f"the shift a = {a} must divide the window length w = {w}")
+    if w // a < 2:
+        raise ValueError(f"w / a must be at least 2, got w = {w}, a = {a}")
+    if not p < w <= W_MAX:
+        raise ValueError(f"w must be in (p, {W_MAX}], got w = {w}, p = {p}")
+    keys = tuple(wtype_key(t) for t in wtypes)
+    if not keys or len(set(keys)) != len(keys):
+        raise ValueError("wtype needs at least one shape, each once")
+    pairs = [window_pair(k, w, a) for k in keys]
+    for k, (ga, gs) in zip(keys, pairs):
+        r = window_rescale(ga, gs, a)
+        if not (np.all(np.isfinite(gs)) and np.all(np.isfinite(r)) and np.all(r > 0)):
+            raise ValueError(f"wtype {k!r} with w = {w}, a = {a}: the overlap-add weight is not "
+                             "positive everywhere")
+    lens = [len(m) for m in masks]
+    starts = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
+    per_shape = int(starts[-1])
+    sig_off, row_tab, gap_start, gap_len = [], [], [], []
+    gap_off, gap_tab, gap_signal, gap_range = [], [], [], []
+    pos = np.arange(w)
+    for k in range(len(keys)):
+        for i, obs in enumerate(masks):
+            obs = np.asarray(obs, bool)
+            base = k * per_shape + int(starts[i])
+            for (g0, g1) in find_gaps(obs):
+                lo, hi = gap_support(g0, g1, w, a)
+                n = hi - lo
+                L = _cdiv(n, a) * a + (_cdiv(w, a) - 1) * a
+                miss_any = np.zeros(L, bool)
+                s0, s1 = max(lo, 0), min(hi, len(obs))
+                miss_any[s0 - lo:s1 - lo] = ~obs[s0:s1]
+                miss = np.zeros(L, bool)
+                miss[g0 - lo:g1 - lo] = True
+                row0 = len(sig_off)
+                for s in range(L // a):
+                    idx = (s * a - w // 2 + pos) % L
+                    m = miss[idx]
+                    if not m.any():
+                        continue
+                    if np.count_nonzero(miss_any[idx]) != np.count_nonzero(m):
+                        raise ValueError(f"signal {i}: a window around the gap [{g0}, {g1}) holds "
+                                         "a second gap; one run of missing samples per window "
+                                         "only")
+                    if m.all():
+                        continue                  # zeros in the sum, counted by the rescale
+                    runs = find_gaps(~m)
+                    if len(runs) != 1:
+                        raise ValueError(f"signal {i}: the gap [{g0}, {g1}) falls into two runs "
+                                         "of one window")
+                    if runs[0][1] - runs[0][0] > GAP_MAX:
+                        raise ValueError(f"signal {i}: a window holds {runs[0][1] - runs[0][0]} "
+                                         f"missing samples, at most {GAP_MAX}")
+                    sig_off.append(base)
+                    row_tab.append((len(obs), lo, n, L, s, k))
+                    gap_start.append(runs[0][0])
+                    gap_len.append(runs[0][1] - runs[0][0])
+                gap_off.append(base + g0)
+                gap_tab.append((g1 - g0, g0 - lo, L, row0, len(sig_off) - row0, k))
+                gap_signal.append(i)
+                gap_range.append((g0, g1))
+    i32 = lambda v, cols=None: np.array(v, dtype=np.int32).reshape((-1,) if cols is None
+                                                                  else (-1, cols))
+    return WindowPlan(keys, w, a, per_shape * len(keys),
+                      np.stack([g for g, _ in pairs]), np.stack([g for _, g in pairs]),
+                      np.array(sig_off, dtype=np.int64), i32(row_tab, 6), i32(gap_start),
+                      i32(gap_len), np.array(gap_off, dtype=np.int64), i32(gap_tab, 6),
+                      i32(gap_signal), i32(gap_range, 2))
+
+
+def janssen_windowed(signal, mask=None, p=512, w=4096, a=1024, wtype="hann", maxit=20,
+                     method="lpc", return_history=False, device="cuda"):
+    """Fill every gap of `signal` by the window-wise Janssen algorithm on the
+    GPU (the reference's segmentation_inp.m on the support train.m:146-172
+    gives it): windows of w samples every a samples around the gap, each with
+    missing samples inpainted by Janssen, overlap-added and rescaled.
+
+    Input layouts, mask / NaN conventions and the return layout are
+    janssen_inpaint's; only missing samples are written.  wtype: "hann", "rect"
+    or "tukey" (any case), or a sequence of them -- then the windows of all
+    shapes share one Janssen launch and a dict {wtype: result} comes back (with
+    return_history: {wtype: (result, history)}).  The history is one dict per
+    gap (signal, start, end, iters: iterations completed per window with a row,
+    history [maxit, gap_len]: the gap after every iteration, NaN from the
+    iteration on that one of its windows did not complete).
+    """
+    import torch
+    from . import ops
+    check_args(p, maxit)
+    method_id(method)
+    single = isinstance(wtype, str)
+    shapes = (wtype,) if single else tuple(wtype)
+    sigs, masks, kind = _normalise(signal, mask)
+    plan = plan_windows(masks, p, w, a, shapes)
+    keys, ns = plan.wtypes, len(sigs)
+    buf = np.concatenate([s for _ in keys for s in sigs]) if ns else np.zeros(0)
+    info = {k: [] for k in keys}
+    if len(plan):
+        dbuf = torch.from_numpy(buf).to(device)
+        sol = ops.janssen_windows(dbuf, plan.sig_off, plan.row_tab, plan.gap_start,
+                                  plan.gap_len, plan.w, plan.a, plan.gana)
+        iters, rhist = ops.janssen(sol, np.full(len(plan), plan.w), plan.gap_start, plan.gap_len,
+                                   p, maxit, return_history=return_history, method=method)
+        hist = ops.janssen_ola(sol, rhist, plan.row_tab, plan.gap_start, plan.gap_len,
+                               plan.gap_off, plan.gap_tab, plan.a, plan.gana, plan.gsyn, dbuf)
+        buf, iters = dbuf.cpu().numpy(), iters.cpu().numpy()
+        hist = hist.cpu().numpy() if hist is not None else None
+        for g in range(len(plan.gap_off)):
+            h, _, _, row0, nrows, k = (int(v) for v in plan.gap_tab[g])
+            info[keys[k]].append({"signal": int(plan.gap_signal[g]),
+                                  "start": int(plan.gap_range[g, 0]),
+                                  "end": int(plan.gap_range[g, 1]),
+                                  "iters": [int(v) for v in iters[row0:row0 + nrows]],
+                                  "history": hist[g, :, :h].copy() if hist is not None else None})
+    out, at = {}, 0
+    for k in keys:
+        res = []
+        for s in sigs:
+            res.append(buf[at:at + len(s)].copy())
+            at += len(s)
+        res = res[0] if kind == "single" else res if kind == "list" else np.stack(res)
+        out[k] = (res, info[k]) if return_history else res
+    return out[keys[0]] if single else out

@@ -2180,3 +2180,104 @@ def ar_extrapolate(sol, n, gap_start, gap_len, p, w, method="lpc"):
     if nseg:
         _T.ar_extrapolate(sol, *dev_i32, int(p), int(w), m, status, ws)
     return status
+
+
+def _window_tables(sol_rows, w, a, sig_off, row_tab, gap_start, gap_len, gana, total):
+    """The host checks the two window-wise launches share -> the tables as
+    numpy (int64 sig_off, int32 the rest).  sig_off None: the overlap-add, which
+    reads no signal through a row."""
+    from . import janssen as _jn
+    w, a = int(w), int(a)
+    if a < 1 or w % a or w // a < 2 or not 2 <= w <= _jn.W_MAX:
+        raise ValueError(f"a must divide w, w / a >= 2 and 2 <= w <= {_jn.W_MAX}")
+    rt = np.ascontiguousarray(np.asarray(row_tab, dtype=np.int32).reshape(-1, 6))
+    gs = np.asarray(gap_start, dtype=np.int32).reshape(-1)
+    gl = np.asarray(gap_len, dtype=np.int32).reshape(-1)
+    so = None if sig_off is None else np.asarray(sig_off, dtype=np.int64).reshape(-1)
+    if not (len(rt) == len(gs) == len(gl) == sol_rows and (so is None or len(so) == sol_rows)):
+        raise ValueError("sig_off, row_tab, gap_start and gap_len need one entry per row")
+    if gana.ndim != 2 or gana.shape[1] != w:
+        raise ValueError("the windows must be [n_shapes, w]")
+    sig_len, _, sup_len, L, win, shape = rt.T.astype(np.int64)
+    if sol_rows and not (np.all(L >= w) and np.all(L % a == 0) and np.all(sup_len >= 0)
+                         and np.all(sup_len <= L) and np.all(win >= 0) and np.all(win * a < L)
+                         and np.all(shape >= 0) and np.all(shape < gana.shape[0])):
+        raise ValueError("row_tab describes a window outside its support")
+    if sol_rows and so is not None and not (np.all(sig_len >= 0) and np.all(so >= 0)
+                                            and np.all(so + sig_len <= total)):
+        raise ValueError("row_tab describes a signal outside the buffer")
+    if sol_rows and not (np.all(gl >= 1) and np.all(gl <= _jn.GAP_MAX) and np.all(gs >= 0)
+                         and np.all(gs.astype(np.int64) + gl <= w)):
+        raise ValueError(f"every run must lie inside its window, 1 <= gap_len <= {_jn.GAP_MAX}")
+    return so, rt, gs, gl
+
+
+def janssen_windows(signals, sig_off, row_tab, gap_start, gap_len, w, a, gana):
+    """ainp_janssen_windows: cut the windows of the window-wise Janssen
+    algorithm out of their signals.  signals: flat float64 cuda buffer, every
+    signal end to end; the tables (host integers, checked here) and gana
+    [n_shapes, w] (host float64) as include/ainp.h describes them.  Returns sol
+    [n_rows, w] float64: signal * gana, zeros on the row's missing run, on the
+    padding and outside the signal."""
+    _req(signals, "signals", dtype=torch.float64)
+    if signals.dim() != 1 or signals.numel() < 1:
+        raise ValueError("signals must be one flat, non-empty buffer")
+    gana = np.ascontiguousarray(gana, dtype=np.float64)
+    nrows = len(np.asarray(sig_off).reshape(-1))
+    so, rt, gs, gl = _window_tables(nrows, w, a, sig_off, row_tab, gap_start, gap_len, gana,
+                                    signals.numel())
+    dv = signals.device
+    sol = torch.empty(nrows, int(w), device=dv, dtype=torch.float64)
+    if nrows:
+        _T.janssen_windows(signals, torch.from_numpy(so).to(dv), torch.from_numpy(rt).to(dv),
+                           torch.from_numpy(gs).to(dv), torch.from_numpy(gl).to(dv), int(a),
+                           torch.from_numpy(gana).to(dv), sol)
+    return sol
+
+
+def janssen_ola(sol, row_history, row_tab, gap_start, gap_len, gap_off, gap_tab, a, gana, gsyn,
+                signals):
+    """ainp_janssen_ola: overlap-add the solved windows `sol` [n_rows, w] back
+    into the gaps of `signals` (flat float64 cuda buffer, written on the
+    missing samples only) and divide by the window weight.  row_history: the
+    history ainp_janssen_ex wrote for the rows, or None; with it returns
+    history [n_gaps, maxit, max h] float64 (NaN beyond a gap's h), else None.
+    Tables as include/ainp.h describes them, host integers checked here."""
+    from . import janssen as _jn
+    _req(sol, "sol", dtype=torch.float64)
+    _req(signals, "signals", dtype=torch.float64)
+    if sol.dim() != 2 or signals.dim() != 1 or signals.numel() < 1:
+        raise ValueError("sol must be [n_rows, w] and signals one flat, non-empty buffer")
+    nrows, w = sol.shape
+    total = signals.numel()
+    gana = np.ascontiguousarray(gana, dtype=np.float64)
+    gsyn = np.ascontiguousarray(gsyn, dtype=np.float64)
+    if gsyn.shape != gana.shape:
+        raise ValueError("gana and gsyn must have one shape")
+    _, rt, gs, gl = _window_tables(nrows, w, a, None, row_tab, gap_start, gap_len, gana, total)
+    go = np.asarray(gap_off, dtype=np.int64).reshape(-1)
+    gt = np.ascontiguousarray(np.asarray(gap_tab, dtype=np.int32).reshape(-1, 6))
+    if len(go) != len(gt):
+        raise ValueError("gap_off and gap_tab need one entry per gap")
+    ngaps = len(go)
+    h, c0, L, row0, nr, shape = gt.T.astype(np.int64)
+    if ngaps and not (np.all(h >= 1) and np.all(h <= _jn.GAP_MAX) and np.all(c0 >= 0)
+                      and np.all(c0 + h <= L) and np.all(L >= w) and np.all(L % int(a) == 0)
+                      and np.all(row0 >= 0) and np.all(nr >= 0) and np.all(row0 + nr <= nrows)
+                      and np.all(shape >= 0) and np.all(shape < gana.shape[0])
+                      and np.all(go >= 0) and np.all(go + h <= total)):
+        raise ValueError(f"gap_tab describes a gap outside its support, its rows or the buffer "
+                         f"(1 <= h <= {_jn.GAP_MAX})")
+    dv = sol.device
+    hist = None
+    if row_history is not None:
+        _req(row_history, "row_history", dtype=torch.float64)
+        if row_history.dim() != 3 or row_history.shape[0] != nrows:
+            raise ValueError("row_history must be [n_rows, maxit, max gap_len]")
+        hist = torch.full((ngaps, row_history.shape[1], int(h.max()) if ngaps else 0),
+                          float("nan"), device=dv, dtype=torch.float64)
+    if ngaps:
+        up = lambda t: torch.from_numpy(t).to(dv)
+        _T.janssen_ola(sol, row_history, up(rt), up(gs), up(gl), up(go), up(gt), int(h.max()),
+                       int(a), up(gana), up(gsyn), signals, hist)
+    return hist

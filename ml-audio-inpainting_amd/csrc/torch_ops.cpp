@@ -274,6 +274,83 @@ void ar_extrapolate(const Tensor& sol, const Tensor& n, const Tensor& gap_start,
       "ar_extrapolate");
 }
 
+// window-wise Janssen: the gather into the batch and the overlap-add out of it
+void janssen_windows(const Tensor& signals, const Tensor& sig_off, const Tensor& row_tab,
+                     const Tensor& gap_start, const Tensor& gap_len, int64_t a,
+                     const Tensor& gana, const Tensor& sol) {
+  GUARD(sol);
+  TORCH_CHECK(sol.dim() == 2, "sol must be [n_rows, w]");
+  TORCH_CHECK(gana.dim() == 2 && gana.size(1) == sol.size(1), "gana must be [n_shapes, w]");
+  TORCH_CHECK(signals.dim() == 1, "signals must be one flat buffer");
+  const int64_t n_rows = sol.size(0), w = sol.size(1);
+  TORCH_CHECK(a >= 1 && a <= INT32_MAX && w <= INT32_MAX && gana.size(0) <= INT32_MAX,
+              "a must be positive");
+  numel_is(sig_off, n_rows, "sig_off");
+  numel_is(row_tab, n_rows * 6, "row_tab");
+  numel_is(gap_start, n_rows, "gap_start");
+  numel_is(gap_len, n_rows, "gap_len");
+  for (const Tensor* t : {&signals, &sig_off, &row_tab, &gap_start, &gap_len, &gana})
+    same_device(sol, *t);
+  chk(ainp_janssen_windows(dev<double>(signals, "signals", at::kDouble), signals.numel(),
+                           dev<int64_t>(sig_off, "sig_off", at::kLong),
+                           dev<int32_t>(row_tab, "row_tab", at::kInt),
+                           dev<int32_t>(gap_start, "gap_start", at::kInt),
+                           dev<int32_t>(gap_len, "gap_len", at::kInt), n_rows, (int)w, (int)a,
+                           dev<double>(gana, "gana", at::kDouble), (int)gana.size(0),
+                           dev<double>(sol, "sol", at::kDouble), w, stream_of(sol)),
+      "janssen_windows");
+}
+
+void janssen_ola(const Tensor& sol, const OptT& row_history, const Tensor& row_tab,
+                 const Tensor& gap_start, const Tensor& gap_len, const Tensor& gap_off,
+                 const Tensor& gap_tab, int64_t h_max, int64_t a, const Tensor& gana,
+                 const Tensor& gsyn, const Tensor& signals, const OptT& history) {
+  GUARD(sol);
+  TORCH_CHECK(sol.dim() == 2, "sol must be [n_rows, w]");
+  TORCH_CHECK(gana.dim() == 2 && gana.size(1) == sol.size(1), "gana must be [n_shapes, w]");
+  TORCH_CHECK(gsyn.sizes() == gana.sizes(), "gsyn must be [n_shapes, w] as gana");
+  TORCH_CHECK(signals.dim() == 1, "signals must be one flat buffer");
+  const int64_t n_rows = sol.size(0), w = sol.size(1), n_gaps = gap_off.numel();
+  TORCH_CHECK(a >= 1 && a <= INT32_MAX && w <= INT32_MAX && gana.size(0) <= INT32_MAX &&
+                  h_max >= 1 && h_max <= INT32_MAX,
+              "a and h_max must be positive");
+  numel_is(row_tab, n_rows * 6, "row_tab");
+  numel_is(gap_start, n_rows, "gap_start");
+  numel_is(gap_len, n_rows, "gap_len");
+  numel_is(gap_tab, n_gaps * 6, "gap_tab");
+  for (const Tensor* t : {&row_tab, &gap_start, &gap_len, &gap_off, &gap_tab, &gana, &gsyn,
+                          &signals})
+    same_device(sol, *t);
+  const double* rh = opt<double>(row_history, "row_history", at::kDouble);
+  double* h = opt<double>(history, "history", at::kDouble);
+  TORCH_CHECK((rh != nullptr) == (h != nullptr), "history needs row_history and the reverse");
+  int64_t maxit = 0, hist_stride = 0, out_stride = 0;
+  if (h) {
+    same_device(sol, *row_history);
+    same_device(sol, *history);
+    TORCH_CHECK(row_history->dim() == 3 && row_history->size(0) == n_rows,
+                "row_history must be [n_rows, maxit, max gap_len], got ", row_history->sizes());
+    maxit = row_history->size(1);
+    hist_stride = row_history->size(2);
+    TORCH_CHECK(history->dim() == 3 && history->size(0) == n_gaps &&
+                    history->size(1) == maxit && history->size(2) >= h_max,
+                "history must be [n_gaps, maxit, >= h_max], got ", history->sizes());
+    TORCH_CHECK(maxit <= INT32_MAX, "maxit too large");
+    out_stride = history->size(2);
+  }
+  chk(ainp_janssen_ola(dev<double>(sol, "sol", at::kDouble), n_rows, w, rh, (int)maxit,
+                       hist_stride, dev<int32_t>(row_tab, "row_tab", at::kInt),
+                       dev<int32_t>(gap_start, "gap_start", at::kInt),
+                       dev<int32_t>(gap_len, "gap_len", at::kInt),
+                       dev<int64_t>(gap_off, "gap_off", at::kLong),
+                       dev<int32_t>(gap_tab, "gap_tab", at::kInt), n_gaps, (int)h_max, (int)w,
+                       (int)a, dev<double>(gana, "gana", at::kDouble),
+                       dev<double>(gsyn, "gsyn", at::kDouble), (int)gana.size(0),
+                       dev<double>(signals, "signals", at::kDouble), signals.numel(), h,
+                       out_stride, stream_of(sol)),
+      "janssen_ola");
+}
+
 // ------------------------------------------------------------------- GEMM
 void gemm(int64_t M, int64_t N, int64_t K, double alpha, at::TensorList A, int64_t sam,
           int64_t sak, int64_t strideA, at::TensorList B, int64_t sbk, int64_t sbn,
@@ -1904,6 +1981,11 @@ TORCH_LIBRARY(ainp, m) {
         "Tensor(b!)? history, Tensor(c!) iters_done, Tensor? workspace, int method=0) -> ()");
   m.def("ar_extrapolate(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int w, "
         "int method, Tensor(b!) status, Tensor? workspace) -> ()");
+  m.def("janssen_windows(Tensor signals, Tensor sig_off, Tensor row_tab, Tensor gap_start, "
+        "Tensor gap_len, int a, Tensor gana, Tensor(a!) sol) -> ()");
+  m.def("janssen_ola(Tensor sol, Tensor? row_history, Tensor row_tab, Tensor gap_start, "
+        "Tensor gap_len, Tensor gap_off, Tensor gap_tab, int h_max, int a, Tensor gana, "
+        "Tensor gsyn, Tensor(a!) signals, Tensor(b!)? history) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
@@ -1992,6 +2074,8 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("mel_inverse", &mel_inverse);
   m.impl("janssen", &janssen);
   m.impl("ar_extrapolate", &ar_extrapolate);
+  m.impl("janssen_windows", &janssen_windows);
+  m.impl("janssen_ola", &janssen_ola);
 }
 
 // The ops write through raw device pointers like the C ABI; autograd is the
@@ -2083,4 +2167,6 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("mel_inverse", torch::CppFunction::makeFallthrough());
   m.impl("janssen", torch::CppFunction::makeFallthrough());
   m.impl("ar_extrapolate", torch::CppFunction::makeFallthrough());
+  m.impl("janssen_windows", torch::CppFunction::makeFallthrough());
+  m.impl("janssen_ola", torch::CppFunction::makeFallthrough());
 }

@@ -190,19 +190,24 @@ def run_janssen_evaluation(input_dir, output_dir, p=512, w=4096, maxit=20):
     return sdrs
 
 
+AR_ALGORITHMS = ("extrapolation", "janssen", "janssen_hann", "janssen_rect", "janssen_tukey")
+
+
 def run_ar_evaluation(input_dir, output_dir, algorithm="janssen", method="lpc", p=512, w=4096,
-                      maxit=20):
+                      maxit=20, a=1024):
     """One cell of models/AudioReg/train.m's table on the clips and the gap of
-    inpaint(): algorithm "janssen" or "extrapolation", estimator "lpc" or
-    "arburg".  Every .flac of input_dir gets the 80 ms gap at 2.0 s, all gaps
-    are filled in one batch, and each result is written as
+    inpaint(): algorithm "extrapolation", "janssen" (gap-wise) or "janssen_hann"
+    / "janssen_rect" / "janssen_tukey" (window-wise, windows of w samples every
+    a samples; a applies to these three only), estimator "lpc" or "arburg".
+    Every .flac of input_dir gets the 80 ms gap at 2.0 s, all gaps are filled
+    in one batch, and each result is written as
     <stem>_<algorithm>[_arburg]_inpainted.flac.  Returns {filename: gap SDR in
     dB}, measured before save_audio's normalisation and 16-bit quantisation.
-    maxit applies to "janssen" only."""
-    from models.AudioReg import ar_extrapolate, gap_sdr, janssen_inpaint
+    maxit does not apply to "extrapolation"."""
+    from models.AudioReg import ar_extrapolate, gap_sdr, janssen_inpaint, janssen_windowed
     from ainp.janssen import method_id
-    if algorithm not in ("janssen", "extrapolation"):
-        raise ValueError(f"algorithm must be 'janssen' or 'extrapolation', got {algorithm!r}")
+    if algorithm not in AR_ALGORITHMS:
+        raise ValueError(f"algorithm must be one of {AR_ALGORITHMS}, got {algorithm!r}")
     suffix = algorithm + ("_arburg" if method_id(method) else "")
     if not os.path.isdir(input_dir):
         print(f"Error: Input directory not found: {input_dir}")
@@ -223,6 +228,9 @@ def run_ar_evaluation(input_dir, output_dir, algorithm="janssen", method="lpc", 
         restored = []
     elif algorithm == "janssen":
         restored = janssen_inpaint(clean, masks, p=p, w=w, maxit=maxit, method=method)
+    elif algorithm.startswith("janssen_"):
+        restored = janssen_windowed(clean, masks, p=p, w=w, a=a, wtype=algorithm[len("janssen_"):],
+                                    maxit=maxit, method=method)
     else:
         restored = ar_extrapolate(clean, masks, p=p, w=w, method=method)
     sdrs = {}

@@ -32,9 +32,22 @@ and the residuals.  Prints one table row and one JSON line per case.
 gap (so the p Burg steps dominate) at n = 9472 and n = 16384 and prints the
 time per Burg step and its slope between successive orders.
 
+--algorithm janssen_hann | janssen_rect | janssen_tukey times the window-wise
+rows (ainp.janssen.janssen_windowed's three launches: the gather
+ainp_janssen_windows, ainp_janssen_ex over the windows, the overlap-add
+ainp_janssen_ola) at w = 4096 and the shift --a (1024) for batches of gaps,
+each launch between its own pair of device events, the same median of --reps
+after one warm-up, next to the gap-wise launch of the same batch.  The tables
+of the gather and the overlap-add are on the device before the timed window;
+the Janssen launch goes through ops.janssen as the gap-wise one does.  It
+prints how many windows (rows) the batch makes and how many rounds of 256
+workgroups (one per CU) that is.  --history also writes every iteration.  No
+CPU run.
+
 Usage: python tools/janssen_bench.py [--reps 5] [--threads 16] [--no-cpu] [--fit]
-           [--method lpc|arburg] [--algorithm janssen|extrapolation]
-           [--orders 256,512] [--batches 1,256] [--burg-steps]
+           [--method lpc|arburg]
+           [--algorithm janssen|extrapolation|janssen_hann|janssen_rect|janssen_tukey]
+           [--a 1024] [--history] [--orders 256,512] [--batches 1,256] [--burg-steps]
 """
 import argparse
 import json
@@ -128,6 +141,76 @@ def time_gpu(batch, n, s, h, p, maxit, reps, method="lpc", algorithm="janssen"):
     return statistics.median(ts), min(ts), max(ts), sol[0].cpu().numpy()
 
 
+def time_windowed(batch, n, s, h, p, maxit, reps, method, wtype, a, history):
+    """One gap [s, s + h) in each of `batch` signals -> {launch: (median, min,
+    max) ms} for the three launches, the number of rows, iterations done."""
+    import torch
+    from ainp import janssen as jn, ops
+    T = torch.ops.ainp
+    sigs = [signal(n, 100 + i % 16) for i in range(batch)]
+    mask = np.ones(n, bool)
+    mask[s:s + h] = False
+    for x in sigs:
+        x[s:s + h] = 0.0
+    plan = jn.plan_windows([mask] * batch, p, W, a, (wtype,))
+    up = lambda t: torch.from_numpy(np.ascontiguousarray(t)).cuda()
+    buf0 = up(np.concatenate(sigs))
+    so, rt, gs, gl = up(plan.sig_off), up(plan.row_tab), up(plan.gap_start), up(plan.gap_len)
+    go, gt, gana, gsyn = up(plan.gap_off), up(plan.gap_tab), up(plan.gana), up(plan.gsyn)
+    rows = len(plan)
+    ts = {"gather": [], "janssen": [], "ola": []}
+    for r in range(reps + 1):
+        buf = buf0.clone()
+        sol = torch.empty(rows, W, device="cuda", dtype=torch.float64)
+        out = torch.full((batch, maxit, h), float("nan"), device="cuda",
+                         dtype=torch.float64) if history else None
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        T.janssen_windows(buf, so, rt, gs, gl, a, gana, sol)
+        ev[1].record()
+        iters, rhist = ops.janssen(sol, [W] * rows, plan.gap_start, plan.gap_len, p, maxit,
+                                   return_history=history, method=method)
+        ev[2].record()
+        T.janssen_ola(sol, rhist, rt, gs, gl, go, gt, h, a, gana, gsyn, buf, out)
+        ev[3].record()
+        torch.cuda.synchronize()
+        if r:
+            for k, name in enumerate(ts):
+                ts[name].append(ev[k].elapsed_time(ev[k + 1]))
+    assert bool(torch.isfinite(buf).all())
+    return ({k: (statistics.median(v), min(v), max(v)) for k, v in ts.items()}, rows,
+            (int(iters.min()), int(iters.max())))
+
+
+def windowed_table(args, n):
+    import torch
+    wtype = args.algorithm[len("janssen_"):]
+    print(f"{torch.cuda.get_device_name(0)}; {args.algorithm} {args.method}, w = {W}, "
+          f"a = {args.a}, n = {n}, h = {H}, maxit = {MAXIT}, history = {args.history}",
+          flush=True)
+    for p in args.orders:
+        for batch in args.batches:
+            t, rows, iters = time_windowed(batch, n, W, H, p, MAXIT, args.reps, args.method,
+                                           wtype, args.a, args.history)
+            gap, glo, ghi, _ = time_gpu(batch, n, W, H, p, MAXIT, args.reps, args.method)
+            rounds = -(-rows // 256)
+            row = dict(algorithm=args.algorithm, method=args.method, p=p, a=args.a, gaps=batch,
+                       rows=rows, workgroup_rounds=rounds, iters_min=iters[0],
+                       iters_max=iters[1], history=args.history,
+                       gap_wise_launch_ms=round(gap, 3), gap_wise_launch_ms_min=round(glo, 3),
+                       gap_wise_launch_ms_max=round(ghi, 3))
+            for k, (med, lo, hi) in t.items():
+                row.update({f"{k}_ms": round(med, 4), f"{k}_ms_min": round(lo, 4),
+                            f"{k}_ms_max": round(hi, 4)})
+            print(f"p {p:5d} gaps {batch:4d} rows {rows:5d} ({rounds} round{'s' * (rounds > 1)})  "
+                  + "  ".join(f"{k} {med:9.4f} ms [{lo:9.4f} .. {hi:9.4f}]"
+                              for k, (med, lo, hi) in t.items())
+                  + f"  gap-wise {gap:9.3f} ms [{glo:9.3f} .. {ghi:9.3f}]  iters {iters}",
+                  flush=True)
+            print(json.dumps(row), flush=True)
+
+
 def _cpu_job(args):
     n, seed, s, h, p, maxit, method, algorithm = args
     if algorithm == "janssen":
@@ -174,7 +257,11 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--fit", action="store_true")
     ap.add_argument("--method", choices=("lpc", "arburg"), default="lpc")
-    ap.add_argument("--algorithm", choices=("janssen", "extrapolation"), default="janssen")
+    ap.add_argument("--algorithm", default="janssen",
+                    choices=("janssen", "extrapolation", "janssen_hann", "janssen_rect",
+                             "janssen_tukey"))
+    ap.add_argument("--a", type=int, default=1024)
+    ap.add_argument("--history", action="store_true")
     ap.add_argument("--orders", type=lambda v: tuple(int(t) for t in v.split(",")), default=ORDERS)
     ap.add_argument("--batches", type=lambda v: tuple(int(t) for t in v.split(",")),
                     default=BATCHES)
@@ -182,6 +269,8 @@ def main():
     args = ap.parse_args()
     n = 2 * W + H
     method, algorithm = args.method, args.algorithm
+    if algorithm.startswith("janssen_"):
+        return windowed_table(args, n)
     cpu = {} if args.no_cpu else cpu_table(n, args.threads, args.orders, method, algorithm)
     import torch
     print(f"{torch.cuda.get_device_name(0)}; {algorithm} {method}, n = {n}, h = {H}, "
