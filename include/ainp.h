@@ -303,6 +303,49 @@ int ainp_janssen_ola(const double* sol, int64_t n_rows, int64_t stride,
                      double* signals, int64_t total, double* history, int64_t out_stride,
                      void* stream);
 
+/* The two SPAIN algorithms (references/spain/aspain.m and sspain.m with
+ * f_update = 'H'): the analysis and the synthesis variant of sparse audio
+ * inpainting by ADMM with a hard threshold. */
+#define AINP_SPAIN_A 0
+#define AINP_SPAIN_S 1
+
+/* SPAIN on a batch of windows, the sparsity row of the same comparison
+ * (references/spain/spain_segmentation.m; csrc/spain.hip).  Float64, one
+ * workgroup per row, the transforms in LDS.  sol [n_rows][stride]: row r holds
+ * w windowed samples with one run of missing samples [gap_start[r],
+ * gap_start[r] + gap_len[r]) (the rows ainp_janssen_windows cuts; the run is
+ * read as zeros).  The frame is the DFT of length M = red * w:
+ *   A x = FFT_M([x; 0]) / sqrt(M),  A* z = first w samples of IFFT_M(z) sqrt(M).
+ * H_k keeps the k largest of the M/2 + 1 half-spectrum coefficients (DC ranked
+ * by half its magnitude, Nyquist by all of it; equal magnitudes: the lower
+ * index first; everything if k >= M/2 + 1) and mirrors the conjugates.  proj
+ * puts the observed samples back.  With x = the row, u = 0, k = s, cnt = 1,
+ * while cnt <= maxit:
+ *   AINP_SPAIN_A (z = A x, u of M coefficients):
+ *     zb = H_k(z + u);  obj = |z - zb|_2 over all M coefficients;  [record, stop]
+ *     x = proj(Re A*(zb - u));  z = A x;  u += z - zb
+ *   AINP_SPAIN_S (u of w samples):
+ *     zb = H_k(A(x - u));  obj = |A* zb - x|_2;  [record, stop]
+ *     xe = Re A* zb;  x = proj(xe + u);  u += xe - x
+ *   then cnt += 1, and k += s if cnt mod r == 0.
+ * [record, stop]: if obj <= the smallest so far, x (as the objective was
+ * evaluated on it) becomes the result; the loop ends if obj <= epsilon.  On
+ * return the run of the row holds the result; observed samples are not
+ * written.  iters int32 [n_rows]: the passes in which the objective was
+ * evaluated.  obj_history (nullable) [n_rows][maxit]: one objective per such
+ * pass, NaN after.  Sums in a fixed order, no float atomics: the same bits on
+ * every call.  A row whose run does not lie in [0, w) or is longer than 2048
+ * is left unwritten with iters = 0.
+ * Supported: w a power of two, 8 <= w <= 4096; red 1, 2 or 4 with red * w <=
+ * 8192; s, r >= 1; 1 <= maxit <= red * w / 2 + 1; epsilon >= 0; stride >= w.
+ * Anything else is AINP_EINVAL without a launch.  workspace: at least
+ * ainp_spain_workspace(...) bytes (0 over the whole range). */
+int ainp_spain(double* sol, int64_t n_rows, int64_t stride, const int32_t* gap_start,
+               const int32_t* gap_len, int w, int red, int algorithm, int s, int r,
+               double epsilon, int maxit, int32_t* iters, double* obj_history, void* workspace,
+               size_t ws_bytes, void* stream);
+size_t ainp_spain_workspace(int64_t n_rows, int w, int red, int algorithm);
+
 /* ------------------------------------------------------------------------ */
 /* fp32 GEMM on MFMA (fp32-accurate bf16 split by default, exact f32 on flag) */
 /* ------------------------------------------------------------------------ */

@@ -265,6 +265,10 @@ _SIGS = {
                                      c_int64, P]),
     "ainp_janssen_ola": (c_int, [P, c_int64, c_int64, P, c_int, c_int64, P, P, P, P, P, c_int64,
                                  c_int, c_int, c_int, P, P, c_int, P, c_int64, P, c_int64, P]),
+    # A-SPAIN / S-SPAIN on a batch of windows (csrc/spain.hip)
+    "ainp_spain": (c_int, [P, c_int64, c_int64, P, P, c_int, c_int, c_int, c_int, c_int, c_double,
+                           c_int, P, P, P, c_size_t, P]),
+    "ainp_spain_workspace": (c_size_t, [c_int64, c_int, c_int, c_int]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -2281,3 +2281,42 @@ def janssen_ola(sol, row_history, row_tab, gap_start, gap_len, gap_off, gap_tab,
         _T.janssen_ola(sol, row_history, up(rt), up(gs), up(gl), up(go), up(gt), int(h.max()),
                        int(a), up(gana), up(gsyn), signals, hist)
     return hist
+
+
+# ================================================================== SPAIN
+def spain(sol, gap_start, gap_len, algorithm="aspain", red=2, s=1, r=1, epsilon=0.1, maxit=None,
+          return_history=False):
+    """ainp_spain: A-SPAIN or S-SPAIN on a batch of windows, float64, one
+    workgroup per row.  sol [n_rows, w] float64 cuda (the rows janssen_windows
+    cut), updated in place: the run [gap_start[i], gap_start[i] + gap_len[i])
+    of row i receives the iterate with the smallest objective, observed samples
+    are not written.  gap_start, gap_len: host integers per row, checked here.
+    maxit None: ceil(floor(w red / 2 + 1) r / s).  Returns (iters int32
+    [n_rows], objective [n_rows, maxit] float64 or None; NaN after a row's
+    last pass)."""
+    from . import spain as _sp
+    _req(sol, "sol", dtype=torch.float64)
+    if sol.dim() != 2:
+        raise ValueError("sol must be [n_rows, w]")
+    nrows, w = sol.shape
+    alg = _sp.algorithm_id(algorithm)
+    maxit = _sp.check_args(w, red, s, r, epsilon, maxit)
+    gs = np.asarray(gap_start, dtype=np.int64).reshape(-1)
+    gl = np.asarray(gap_len, dtype=np.int64).reshape(-1)
+    if gs.size != nrows or gl.size != nrows:
+        raise ValueError("gap_start and gap_len need one entry per row")
+    if nrows and not (np.all(gl >= 1) and np.all(gl <= _sp.GAP_MAX) and np.all(gs >= 0)
+                      and np.all(gs + gl <= w)):
+        raise ValueError(f"every run must lie inside its window, 1 <= gap_len <= {_sp.GAP_MAX}")
+    dv = sol.device
+    iters = torch.zeros(nrows, device=dv, dtype=torch.int32)
+    hist = None
+    if return_history:
+        hist = torch.full((nrows, maxit), float("nan"), device=dv, dtype=torch.float64)
+    ws_bytes = _lib.lib.ainp_spain_workspace(nrows, int(w), int(red), alg)
+    ws = torch.empty(ws_bytes, device=dv, dtype=torch.uint8) if ws_bytes else None
+    if nrows:
+        _T.spain(sol, torch.from_numpy(gs.astype(np.int32)).to(dv),
+                 torch.from_numpy(gl.astype(np.int32)).to(dv), int(red), alg, int(s), int(r),
+                 float(epsilon), maxit, iters, hist, ws)
+    return iters, hist

@@ -351,6 +351,41 @@ void janssen_ola(const Tensor& sol, const OptT& row_history, const Tensor& row_t
       "janssen_ola");
 }
 
+// SPAIN on the rows janssen_windows cut
+void spain(const Tensor& sol, const Tensor& gap_start, const Tensor& gap_len, int64_t red,
+           int64_t algorithm, int64_t s, int64_t r, double epsilon, int64_t maxit,
+           const Tensor& iters, const OptT& obj_history, const OptT& workspace) {
+  GUARD(sol);
+  TORCH_CHECK(sol.dim() == 2, "sol must be [n_rows, w]");
+  TORCH_CHECK(algorithm == AINP_SPAIN_A || algorithm == AINP_SPAIN_S,
+              "algorithm must be 0 (aspain) or 1 (sspain)");
+  const int64_t n_rows = sol.size(0), w = sol.size(1);
+  numel_is(gap_start, n_rows, "gap_start");
+  numel_is(gap_len, n_rows, "gap_len");
+  numel_is(iters, n_rows, "iters");
+  same_device(sol, gap_start);
+  same_device(sol, gap_len);
+  same_device(sol, iters);
+  TORCH_CHECK(w <= INT32_MAX && red >= 1 && red <= INT32_MAX && s >= 1 && s <= INT32_MAX &&
+                  r >= 1 && r <= INT32_MAX && maxit >= 1 && maxit <= INT32_MAX,
+              "red, s, r and maxit must be positive");
+  double* h = opt<double>(obj_history, "obj_history", at::kDouble);
+  if (h) {
+    same_device(sol, *obj_history);
+    TORCH_CHECK(obj_history->dim() == 2 && obj_history->size(0) == n_rows &&
+                    obj_history->size(1) == maxit,
+                "obj_history must be [n_rows, maxit], got ", obj_history->sizes());
+  }
+  uint8_t* ws = opt<uint8_t>(workspace, "workspace", at::kByte);
+  if (ws) same_device(sol, *workspace);
+  chk(ainp_spain(dev<double>(sol, "sol", at::kDouble), n_rows, w,
+                 dev<int32_t>(gap_start, "gap_start", at::kInt),
+                 dev<int32_t>(gap_len, "gap_len", at::kInt), (int)w, (int)red, (int)algorithm,
+                 (int)s, (int)r, epsilon, (int)maxit, dev<int32_t>(iters, "iters", at::kInt), h, ws,
+                 ws ? (size_t)workspace->numel() : 0, stream_of(sol)),
+      "spain");
+}
+
 // ------------------------------------------------------------------- GEMM
 void gemm(int64_t M, int64_t N, int64_t K, double alpha, at::TensorList A, int64_t sam,
           int64_t sak, int64_t strideA, at::TensorList B, int64_t sbk, int64_t sbn,
@@ -1986,6 +2021,9 @@ TORCH_LIBRARY(ainp, m) {
   m.def("janssen_ola(Tensor sol, Tensor? row_history, Tensor row_tab, Tensor gap_start, "
         "Tensor gap_len, Tensor gap_off, Tensor gap_tab, int h_max, int a, Tensor gana, "
         "Tensor gsyn, Tensor(a!) signals, Tensor(b!)? history) -> ()");
+  m.def("spain(Tensor(a!) sol, Tensor gap_start, Tensor gap_len, int red, int algorithm, int s, "
+        "int r, float epsilon, int maxit, Tensor(b!) iters, Tensor(c!)? obj_history, "
+        "Tensor? workspace) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
@@ -2076,6 +2114,7 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("ar_extrapolate", &ar_extrapolate);
   m.impl("janssen_windows", &janssen_windows);
   m.impl("janssen_ola", &janssen_ola);
+  m.impl("spain", &spain);
 }
 
 // The ops write through raw device pointers like the C ABI; autograd is the
@@ -2169,4 +2208,5 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("ar_extrapolate", torch::CppFunction::makeFallthrough());
   m.impl("janssen_windows", torch::CppFunction::makeFallthrough());
   m.impl("janssen_ola", torch::CppFunction::makeFallthrough());
+  m.impl("spain", torch::CppFunction::makeFallthrough());
 }

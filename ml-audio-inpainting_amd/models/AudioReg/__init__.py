@@ -1,11 +1,14 @@
-"""models/AudioReg of the reference (the autoregressive baselines of the model
+"""models/AudioReg of the reference (the signal-processing rows of the model
 comparison; MATLAB there): the gap-wise Janssen algorithm of
 utils/janssen_inp.m, its window-wise form of utils/segmentation_inp.m (Hann,
 rectangular and Tukey windows) and the forward/backward extrapolation of
 utils/arinpaint.m as train.m drives them, with the "lpc" or the "arburg"
 estimator, on the GPU (ainp/janssen.py -> csrc/janssen.hip,
-csrc/janssen_windows.hip, csrc/ar_extrapolate.hip), and the gap SDR of
-train.m:196 / model_eval.m:60."""
+csrc/janssen_windows.hip, csrc/ar_extrapolate.hip); the sparsity-based A-SPAIN
+and S-SPAIN of references/spain (ainp/spain.py -> csrc/spain.hip between the
+same gather and overlap-add); and the gap SDR of train.m:196 /
+model_eval.m:60."""
 from ainp.janssen import ar_extrapolate, gap_sdr, janssen_inpaint, janssen_windowed
+from ainp.spain import spain_inpaint
 
-__all__ = ["janssen_inpaint", "janssen_windowed", "ar_extrapolate", "gap_sdr"]
+__all__ = ["janssen_inpaint", "janssen_windowed", "ar_extrapolate", "spain_inpaint", "gap_sdr"]

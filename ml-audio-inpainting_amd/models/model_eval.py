@@ -23,6 +23,8 @@ Follows models/model_eval.py:23-227 step by step, on the MI355X kernels:
                             <name>_janssen_inpainted.flac and the gap SDRs
   run_ar_evaluation         any cell of models/AudioReg/train.m's table: Janssen
                             or forward/backward extrapolation, "lpc" or "arburg"
+  run_spain_evaluation      the sparsity row they are compared against
+                            (models/AudioReg/references/spain): A-SPAIN or S-SPAIN
 Spectrogram plots (:157-162,180-185) are out of scope (plotting).  The ISTFT
 runs on the GPU (ainp_istft); output length hop * (T - 1), as librosa's.
 """
@@ -236,6 +238,45 @@ def run_ar_evaluation(input_dir, output_dir, algorithm="janssen", method="lpc", 
     sdrs = {}
     for filename, x, y, m, sr in zip(flac_files, clean, restored, masks, srs):
         out = os.path.join(output_dir, f"{os.path.splitext(filename)[0]}_{suffix}_inpainted.flac")
+        utils.save_audio(y, file_path=out, sample_rate=sr)
+        sdrs[filename] = gap_sdr(x, y, m)
+    return sdrs
+
+
+SPAIN_ALGORITHMS = ("aspain", "sspain")
+
+
+def run_spain_evaluation(input_dir, output_dir, algorithm="aspain", w=4096, a=1024, **solver):
+    """The sparsity row of the same comparison (references/spain) on the clips
+    and the gap of inpaint(): algorithm "aspain" or "sspain", Hann windows of w
+    samples every a samples, **solver handed to spain_inpaint (red, s, r,
+    epsilon, maxit).  Every .flac of input_dir gets the 80 ms gap at 2.0 s, all
+    gaps are filled in one batch, and each result is written as
+    <stem>_<algorithm>_inpainted.flac.  Returns {filename: gap SDR in dB},
+    measured before save_audio's normalisation and 16-bit quantisation."""
+    from models.AudioReg import gap_sdr, spain_inpaint
+    if algorithm not in SPAIN_ALGORITHMS:
+        raise ValueError(f"algorithm must be one of {SPAIN_ALGORITHMS}, got {algorithm!r}")
+    if not os.path.isdir(input_dir):
+        print(f"Error: Input directory not found: {input_dir}")
+        return
+    os.makedirs(output_dir, exist_ok=True)
+    if not torch.cuda.is_available():
+        raise RuntimeError("model_eval runs on the MI355X kernels: no GPU visible")
+    flac_files = sorted(f for f in os.listdir(input_dir) if f.lower().endswith(".flac"))
+    print(f"Found {len(flac_files)} .flac files in {input_dir}")
+    clean, masks, srs = [], [], []
+    for filename in flac_files:
+        audio, sr = utils.load_audio(os.path.join(input_dir, filename))
+        mask_td, _ = utils.create_gap_mask(len(audio), GAP_LEN_S, sr, gap_start_s=GAP_START_S)
+        clean.append(audio.astype(np.float64))
+        masks.append(mask_td > 0)
+        srs.append(sr)
+    restored = spain_inpaint(clean, masks, algorithm=algorithm, w=w, a=a, **solver) if clean else []
+    sdrs = {}
+    for filename, x, y, m, sr in zip(flac_files, clean, restored, masks, srs):
+        out = os.path.join(output_dir,
+                           f"{os.path.splitext(filename)[0]}_{algorithm}_inpainted.flac")
         utils.save_audio(y, file_path=out, sample_rate=sr)
         sdrs[filename] = gap_sdr(x, y, m)
     return sdrs
