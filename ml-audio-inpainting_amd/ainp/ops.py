@@ -25,7 +25,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import janssen as _jn
 from . import mel as _mel
+from . import spain as _sp
 
 # AINP_TORCH_OPS: another build of the same registration (e.g. the UBSan build
 # libainp_torch_ubsan.so that tests/test_gpu_sanitize.py loads)
@@ -2107,10 +2109,32 @@ def mel_to_linear(M, sr=22050, n_fft=2048, n_mels=128, fmin=0.0, fmax=None, powe
 
 
 # ================================================================ Janssen
+def _check_runs(gap_start, gap_len, length, what):
+    """Every row's missing run lies inside the row (`length`: one number, or one
+    per row) and has 1 <= gap_len <= GAP_MAX; `what` names run and row."""
+    gs, gl = np.asarray(gap_start, np.int64), np.asarray(gap_len, np.int64)
+    if not (np.all(gl >= 1) and np.all(gl <= _jn.GAP_MAX) and np.all(gs >= 0)
+            and np.all(gs + gl <= length)):
+        raise ValueError(f"every {what}, 1 <= gap_len <= {_jn.GAP_MAX}")
+
+
+def _dev_i32(table, device):
+    return torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).to(device)
+
+
+def _row_outputs(device, nrows, history_shape, ws_bytes):
+    """What a launch over nrows rows writes -> (zeroed int32 [nrows], float64
+    NaN tensor of history_shape or None, ws_bytes of workspace or None)."""
+    count = torch.zeros(nrows, device=device, dtype=torch.int32)
+    hist = (torch.full(history_shape, float("nan"), device=device, dtype=torch.float64)
+            if history_shape is not None else None)
+    ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8) if ws_bytes else None
+    return count, hist, ws
+
+
 def _ar_tables(sol, n, gap_start, gap_len, p):
     """The host checks the two AR launches share -> (nseg, stride, [n, gap_start,
     gap_len] as int64 numpy)."""
-    from . import janssen as _jn
     _req(sol, "sol", dtype=torch.float64)
     if sol.dim() != 2:
         raise ValueError("sol must be [n_segments, stride]")
@@ -2121,9 +2145,7 @@ def _ar_tables(sol, n, gap_start, gap_len, p):
     nn, gs, gl = tabs
     if nseg and not (np.all(nn > p) and np.all(nn <= min(stride, _jn.N_MAX))):
         raise ValueError(f"every segment length must be in (p, min(stride, {_jn.N_MAX})]")
-    if nseg and not (np.all(gl >= 1) and np.all(gl <= _jn.GAP_MAX) and np.all(gs >= 0)
-                     and np.all(gs + gl <= nn)):
-        raise ValueError(f"every gap must lie inside its segment, 1 <= gap_len <= {_jn.GAP_MAX}")
+    _check_runs(gs, gl, nn, "gap must lie inside its segment")
     return nseg, stride, tabs
 
 
@@ -2136,20 +2158,16 @@ def janssen(sol, n, gap_start, gap_len, p, maxit, return_history=False, method="
     AR estimator, "lpc" or "arburg".  Returns (iters_done int32 [n_segments],
     history [n_segments, maxit, max gap_len] float64 or None; NaN where an
     iteration was not completed)."""
-    from . import janssen as _jn
     _jn.check_args(p, maxit)
     m = _jn.method_id(method)
     nseg, stride, tabs = _ar_tables(sol, n, gap_start, gap_len, p)
     nn, gs, gl = tabs
-    dev_i32 = [torch.from_numpy(t.astype(np.int32)).to(sol.device) for t in tabs]
-    iters = torch.zeros(nseg, device=sol.device, dtype=torch.int32)
-    hist = None
-    if return_history:
-        hist = torch.full((nseg, int(maxit), int(gl.max()) if nseg else 0), float("nan"),
-                          device=sol.device, dtype=torch.float64)
+    dev_i32 = [_dev_i32(t, sol.device) for t in tabs]
+    h_max = int(gl.max()) if nseg else 0
     ws_bytes = _lib.lib.ainp_janssen_ex_workspace(nseg, int(nn.max()) if nseg else 0, int(p),
-                                                  int(gl.max()) if nseg else 0, m)
-    ws = torch.empty(ws_bytes, device=sol.device, dtype=torch.uint8) if ws_bytes else None
+                                                  h_max, m)
+    iters, hist, ws = _row_outputs(sol.device, nseg,
+                                   (nseg, int(maxit), h_max) if return_history else None, ws_bytes)
     if nseg:
         _T.janssen(sol, *dev_i32, int(p), int(maxit), hist, iters, ws, m)
     return iters, hist
@@ -2162,7 +2180,6 @@ def ar_extrapolate(sol, n, gap_start, gap_len, p, w, method="lpc"):
     context is at most w samples and must be longer than p.  method: "lpc" or
     "arburg".  Returns status int32 [n_segments]: 1 filled, 0 filled with a
     side that had a constant context and predicted its mean."""
-    from . import janssen as _jn
     _jn.check_args(p, 1)
     if int(w) < 1:
         raise ValueError("w must be positive")
@@ -2171,12 +2188,11 @@ def ar_extrapolate(sol, n, gap_start, gap_len, p, w, method="lpc"):
     nn, gs, gl = tabs
     if nseg and not (np.all(np.minimum(gs, w) > p) and np.all(np.minimum(nn - gs - gl, w) > p)):
         raise ValueError("both contexts of every gap (clipped to w) must be longer than p")
-    dev_i32 = [torch.from_numpy(t.astype(np.int32)).to(sol.device) for t in tabs]
-    status = torch.zeros(nseg, device=sol.device, dtype=torch.int32)
+    dev_i32 = [_dev_i32(t, sol.device) for t in tabs]
     # the launch sizes its scratch by the stride alone (the tables are on the device)
     ws_bytes = _lib.lib.ainp_ar_extrapolate_workspace(nseg, min(stride, _jn.N_MAX), int(p),
                                                       _jn.GAP_MAX, m)
-    ws = torch.empty(ws_bytes, device=sol.device, dtype=torch.uint8) if ws_bytes else None
+    status, _, ws = _row_outputs(sol.device, nseg, None, ws_bytes)
     if nseg:
         _T.ar_extrapolate(sol, *dev_i32, int(p), int(w), m, status, ws)
     return status
@@ -2186,7 +2202,6 @@ def _window_tables(sol_rows, w, a, sig_off, row_tab, gap_start, gap_len, gana, t
     """The host checks the two window-wise launches share -> the tables as
     numpy (int64 sig_off, int32 the rest).  sig_off None: the overlap-add, which
     reads no signal through a row."""
-    from . import janssen as _jn
     w, a = int(w), int(a)
     if a < 1 or w % a or w // a < 2 or not 2 <= w <= _jn.W_MAX:
         raise ValueError(f"a must divide w, w / a >= 2 and 2 <= w <= {_jn.W_MAX}")
@@ -2206,9 +2221,7 @@ def _window_tables(sol_rows, w, a, sig_off, row_tab, gap_start, gap_len, gana, t
     if sol_rows and so is not None and not (np.all(sig_len >= 0) and np.all(so >= 0)
                                             and np.all(so + sig_len <= total)):
         raise ValueError("row_tab describes a signal outside the buffer")
-    if sol_rows and not (np.all(gl >= 1) and np.all(gl <= _jn.GAP_MAX) and np.all(gs >= 0)
-                         and np.all(gs.astype(np.int64) + gl <= w)):
-        raise ValueError(f"every run must lie inside its window, 1 <= gap_len <= {_jn.GAP_MAX}")
+    _check_runs(gs, gl, w, "run must lie inside its window")
     return so, rt, gs, gl
 
 
@@ -2229,8 +2242,8 @@ def janssen_windows(signals, sig_off, row_tab, gap_start, gap_len, w, a, gana):
     dv = signals.device
     sol = torch.empty(nrows, int(w), device=dv, dtype=torch.float64)
     if nrows:
-        _T.janssen_windows(signals, torch.from_numpy(so).to(dv), torch.from_numpy(rt).to(dv),
-                           torch.from_numpy(gs).to(dv), torch.from_numpy(gl).to(dv), int(a),
+        _T.janssen_windows(signals, torch.from_numpy(so).to(dv), _dev_i32(rt, dv),
+                           _dev_i32(gs, dv), _dev_i32(gl, dv), int(a),
                            torch.from_numpy(gana).to(dv), sol)
     return sol
 
@@ -2243,7 +2256,6 @@ def janssen_ola(sol, row_history, row_tab, gap_start, gap_len, gap_off, gap_tab,
     history ainp_janssen_ex wrote for the rows, or None; with it returns
     history [n_gaps, maxit, max h] float64 (NaN beyond a gap's h), else None.
     Tables as include/ainp.h describes them, host integers checked here."""
-    from . import janssen as _jn
     _req(sol, "sol", dtype=torch.float64)
     _req(signals, "signals", dtype=torch.float64)
     if sol.dim() != 2 or signals.dim() != 1 or signals.numel() < 1:
@@ -2278,8 +2290,9 @@ def janssen_ola(sol, row_history, row_tab, gap_start, gap_len, gap_off, gap_tab,
                           float("nan"), device=dv, dtype=torch.float64)
     if ngaps:
         up = lambda t: torch.from_numpy(t).to(dv)
-        _T.janssen_ola(sol, row_history, up(rt), up(gs), up(gl), up(go), up(gt), int(h.max()),
-                       int(a), up(gana), up(gsyn), signals, hist)
+        _T.janssen_ola(sol, row_history, _dev_i32(rt, dv), _dev_i32(gs, dv), _dev_i32(gl, dv),
+                       up(go), _dev_i32(gt, dv), int(h.max()), int(a), up(gana), up(gsyn),
+                       signals, hist)
     return hist
 
 
@@ -2294,7 +2307,6 @@ def spain(sol, gap_start, gap_len, algorithm="aspain", red=2, s=1, r=1, epsilon=
     maxit None: ceil(floor(w red / 2 + 1) r / s).  Returns (iters int32
     [n_rows], objective [n_rows, maxit] float64 or None; NaN after a row's
     last pass)."""
-    from . import spain as _sp
     _req(sol, "sol", dtype=torch.float64)
     if sol.dim() != 2:
         raise ValueError("sol must be [n_rows, w]")
@@ -2305,18 +2317,11 @@ def spain(sol, gap_start, gap_len, algorithm="aspain", red=2, s=1, r=1, epsilon=
     gl = np.asarray(gap_len, dtype=np.int64).reshape(-1)
     if gs.size != nrows or gl.size != nrows:
         raise ValueError("gap_start and gap_len need one entry per row")
-    if nrows and not (np.all(gl >= 1) and np.all(gl <= _sp.GAP_MAX) and np.all(gs >= 0)
-                      and np.all(gs + gl <= w)):
-        raise ValueError(f"every run must lie inside its window, 1 <= gap_len <= {_sp.GAP_MAX}")
+    _check_runs(gs, gl, w, "run must lie inside its window")
     dv = sol.device
-    iters = torch.zeros(nrows, device=dv, dtype=torch.int32)
-    hist = None
-    if return_history:
-        hist = torch.full((nrows, maxit), float("nan"), device=dv, dtype=torch.float64)
-    ws_bytes = _lib.lib.ainp_spain_workspace(nrows, int(w), int(red), alg)
-    ws = torch.empty(ws_bytes, device=dv, dtype=torch.uint8) if ws_bytes else None
+    iters, hist, ws = _row_outputs(dv, nrows, (nrows, maxit) if return_history else None,
+                                   _lib.lib.ainp_spain_workspace(nrows, int(w), int(red), alg))
     if nrows:
-        _T.spain(sol, torch.from_numpy(gs.astype(np.int32)).to(dv),
-                 torch.from_numpy(gl.astype(np.int32)).to(dv), int(red), alg, int(s), int(r),
+        _T.spain(sol, _dev_i32(gs, dv), _dev_i32(gl, dv), int(red), alg, int(s), int(r),
                  float(epsilon), maxit, iters, hist, ws)
     return iters, hist

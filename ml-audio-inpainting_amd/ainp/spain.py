@@ -12,8 +12,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from .janssen import (GAP_MAX, WindowPlan, _cdiv, _normalise, find_gaps, window_pair,
-                      window_rescale)
+from .gaps import (_cdiv, _normalise, check_shift, find_gaps, restack, solve_windows, window_pairs,
+                   window_plan, window_rows)
+from .janssen import GAP_MAX
 
 ALGORITHMS = {"aspain": 0, "sspain": 1}      # AINP_SPAIN_A, AINP_SPAIN_S
 W_MIN, W_MAX, M_MAX = 8, 4096, 8192          # csrc/spain.hip SP_WMIN, SP_WMAX, SP_MMAX
@@ -34,22 +35,22 @@ def default_maxit(w, red=2, s=1, r=1):
     return min(_cdiv((w * red // 2 + 1) * r, s), w * red // 2 + 1)
 
 
-def check_window(w, a):
-    w, a = int(w), int(a)
+def _check_w(w):
     if not (W_MIN <= w <= W_MAX and w & (w - 1) == 0):
         raise ValueError(f"w must be a power of two in [{W_MIN}, {W_MAX}], got w = {w}")
-    if a < 1 or w % a:
-        raise ValueError(f"the shift a = {a} must divide the window length w = {w}")
-    if w // a < 2:
-        raise ValueError(f"w / a must be at least 2, got w = {w}, a = {a}")
+
+
+def check_window(w, a):
+    w, a = int(w), int(a)
+    _check_w(w)
+    check_shift(w, a)
     return w, a
 
 
 def check_args(w, red=2, s=1, r=1, epsilon=0.1, maxit=None):
     """The solver's range (ainp_spain's) -> maxit with the default filled in."""
     w, red = int(w), int(red)
-    if not (W_MIN <= w <= W_MAX and w & (w - 1) == 0):
-        raise ValueError(f"w must be a power of two in [{W_MIN}, {W_MAX}], got w = {w}")
+    _check_w(w)
     if red not in REDS or red * w > M_MAX:
         raise ValueError(f"red must be one of {REDS} with red * w <= {M_MAX}, got red = {red}")
     if int(s) < 1 or int(r) < 1:
@@ -73,57 +74,23 @@ def plan_spain_windows(masks, w=4096, a=1024):
     covered: w no power of two in [8, 4096], a not dividing w, w / a < 2, a
     window that holds a second gap or two runs, a run of more than 2048."""
     w, a = check_window(w, a)
-    gana, gsyn = window_pair("hann", w, a)
-    resc = window_rescale(gana, gsyn, a)
-    if not (np.all(np.isfinite(gsyn)) and np.all(np.isfinite(resc)) and np.all(resc > 0)):
-        raise ValueError(f"w = {w}, a = {a}: the overlap-add weight is not positive everywhere")
-    lens = [len(m) for m in masks]
-    starts = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
-    sig_off, row_tab, gap_start, gap_len = [], [], [], []
-    gap_off, gap_tab, gap_signal, gap_range = [], [], [], []
-    pos = np.arange(w)
+    pairs = window_pairs(("hann",), w, a, name_shape=False)
+    gaps = []
     for i, obs in enumerate(masks):
         obs = np.asarray(obs, bool)
-        Ls, base = len(obs), int(starts[i])
+        Ls = len(obs)
         L = _cdiv(Ls, a) * a + (_cdiv(w, a) - 1) * a
         miss_any = np.zeros(L, bool)
         miss_any[:Ls] = ~obs
         for (g0, g1) in find_gaps(obs):
             if g1 - g0 > GAP_MAX:
                 raise ValueError(f"signal {i}: gap [{g0}, {g1}) is longer than {GAP_MAX} samples")
-            miss = np.zeros(L, bool)
-            miss[g0:g1] = True
-            row0 = len(sig_off)
             # the windows that can reach the gap: |n a - c| <= w / 2 for a sample c of it
             n_lo, n_hi = (g0 - w // 2) // a, _cdiv(g1 + w // 2, a)
-            for n in sorted({n % (L // a) for n in range(n_lo, n_hi + 1)}):
-                idx = (n * a - w // 2 + pos) % L
-                m = miss[idx]
-                if not m.any():
-                    continue
-                if np.count_nonzero(miss_any[idx]) != np.count_nonzero(m):
-                    raise ValueError(f"signal {i}: a window around the gap [{g0}, {g1}) holds a "
-                                     "second gap; one run of missing samples per window only")
-                if m.all():
-                    continue                      # zeros in the overlap-add
-                runs = find_gaps(~m)
-                if len(runs) != 1:
-                    raise ValueError(f"signal {i}: the gap [{g0}, {g1}) falls into two runs of "
-                                     "one window")
-                sig_off.append(base)
-                row_tab.append((Ls, 0, Ls, L, n, 0))
-                gap_start.append(runs[0][0])
-                gap_len.append(runs[0][1] - runs[0][0])
-            gap_off.append(base + g0)
-            gap_tab.append((g1 - g0, g0, L, row0, len(sig_off) - row0, 0))
-            gap_signal.append(i)
-            gap_range.append((g0, g1))
-    i32 = lambda v, cols=None: np.array(v, dtype=np.int32).reshape((-1,) if cols is None
-                                                                  else (-1, cols))
-    return WindowPlan(("hann",), w, a, int(starts[-1]), gana[None], gsyn[None],
-                      np.array(sig_off, dtype=np.int64), i32(row_tab, 6), i32(gap_start),
-                      i32(gap_len), np.array(gap_off, dtype=np.int64), i32(gap_tab, 6),
-                      i32(gap_signal), i32(gap_range, 2))
+            windows = sorted({n % (L // a) for n in range(n_lo, n_hi + 1)})
+            gaps.append((0, i, g0, g1, 0, Ls, L,
+                         list(window_rows(miss_any, g0, w, a, windows, i, g0, g1))))
+    return window_plan(("hann",), w, a, pairs, masks, gaps)
 
 
 def spain_inpaint(signal, mask=None, algorithm="aspain", w=4096, a=1024, wtype="hann", red=2,
@@ -143,7 +110,6 @@ def spain_inpaint(signal, mask=None, algorithm="aspain", w=4096, a=1024, wtype="
     objective [n_windows, maxit]: the objective of every pass, NaN after the
     last).
     """
-    import torch
     from . import ops
     algorithm_id(algorithm)
     if not (isinstance(wtype, str) and wtype.lower() == "hann"):
@@ -153,21 +119,14 @@ def spain_inpaint(signal, mask=None, algorithm="aspain", w=4096, a=1024, wtype="
     maxit = check_args(w, red, s, r, epsilon, maxit)
     sigs, masks, kind = _normalise(signal, mask)
     plan = plan_spain_windows(masks, w, a)
+    (res,), iters, obj = solve_windows(
+        sigs, plan, device, per_gap=False,
+        solve=lambda sol: ops.spain(sol, plan.gap_start, plan.gap_len, algorithm=algorithm,
+                                    red=red, s=s, r=r, epsilon=epsilon, maxit=maxit,
+                                    return_history=return_history))
+    if obj is None and return_history:
+        obj = np.zeros((0, maxit))           # an empty plan
     info = []
-    buf = np.concatenate(sigs) if sigs else np.zeros(0)
-    iters = np.zeros(0, np.int32)
-    obj = np.zeros((0, maxit)) if return_history else None
-    if len(plan):
-        dbuf = torch.from_numpy(buf).to(device)
-        sol = ops.janssen_windows(dbuf, plan.sig_off, plan.row_tab, plan.gap_start,
-                                  plan.gap_len, plan.w, plan.a, plan.gana)
-        iters, obj = ops.spain(sol, plan.gap_start, plan.gap_len, algorithm=algorithm, red=red,
-                               s=s, r=r, epsilon=epsilon, maxit=maxit,
-                               return_history=return_history)
-        ops.janssen_ola(sol, None, plan.row_tab, plan.gap_start, plan.gap_len, plan.gap_off,
-                        plan.gap_tab, plan.a, plan.gana, plan.gsyn, dbuf)
-        buf, iters = dbuf.cpu().numpy(), iters.cpu().numpy()
-        obj = obj.cpu().numpy() if obj is not None else None
     for g in range(len(plan.gap_off)):
         h, _, _, row0, nrows, _ = (int(v) for v in plan.gap_tab[g])
         g0, g1 = (int(v) for v in plan.gap_range[g])
@@ -175,9 +134,5 @@ def spain_inpaint(signal, mask=None, algorithm="aspain", w=4096, a=1024, wtype="
         info.append({"signal": int(plan.gap_signal[g]), "start": g0, "end": g1,
                      "iters": [int(v) for v in iters[row0:row0 + nrows]],
                      "objective": obj[row0:row0 + nrows].copy() if obj is not None else None})
-    res, at = [], 0
-    for sg in sigs:
-        res.append(buf[at:at + len(sg)].copy())
-        at += len(sg)
-    out = res[0] if kind == "single" else res if kind == "list" else np.stack(res)
+    out = restack(res, kind)
     return (out, info) if return_history else out

@@ -6,15 +6,12 @@
 #pragma once
 #include <math.h>
 
+#include "ar_limits.h"
 #include "common.h"
 
 namespace ainp {
 
 constexpr int JN_THREADS = 256;
-constexpr int JN_PMAX = 3072;
-constexpr int JN_NMAX = 16384;
-constexpr int JN_HMAX = 2048;
-constexpr int JN_ITMAX = 1000;
 
 // The Burg estimator keeps its two error vectors in registers: 512 lanes, 32
 // consecutive elements of each vector per lane (2 x 32 doubles = 128 VGPRs of

@@ -12,14 +12,12 @@
 // per-row table entries are uniform over the workgroup (scalar loads).
 #include <algorithm>
 
+#include "ar_limits.h"
 #include "common.h"
 
 namespace ainp {
 
 constexpr int JW_THREADS = 256;
-constexpr int JW_WMAX = 16384;   // janssen.hip JN_NMAX
-constexpr int JW_HMAX = 2048;    // janssen.hip JN_HMAX
-constexpr int JW_ITMAX = 1000;   // janssen.hip JN_ITMAX
 
 // row_tab[r]: the window of batch row r
 struct JwRow {
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(JW_THREADS) void janssen_ola_kernel(
     const int64_t r = t.row0 + k;
     const int i = jw_mod(c - row_tab[r].win * a + w / 2, t.L);
     const int q = i - gap_start[r];
-    if (i >= w || q < 0 || q >= gap_len[r] || q >= JW_HMAX) continue;
+    if (i >= w || q < 0 || q >= gap_len[r] || q >= JN_HMAX) continue;
     const double z = final_ ? sol[r * stride + i]
                             : (q < hist_stride ? row_history[(r * maxit + it) * hist_stride + q]
                                                : 0.0);
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(JW_THREADS) void janssen_ola_kernel(
 using namespace ainp;
 
 static bool jw_shape_ok(int w, int a, int n_shapes) {
-  return w >= 2 && w <= JW_WMAX && a >= 1 && w % a == 0 && w / a >= 2 && n_shapes >= 1;
+  return w >= 2 && w <= JN_NMAX && a >= 1 && w % a == 0 && w / a >= 2 && n_shapes >= 1;
 }
 
 extern "C" int ainp_janssen_windows(const double* signals, int64_t total, const int64_t* sig_off,
@@ -165,12 +163,12 @@ extern "C" int ainp_janssen_ola(const double* sol, int64_t n_rows, int64_t strid
     return record_msg("ainp_janssen_ola: bad argument (a divides w, w / a >= 2, "
                       "2 <= w <= 16384, n_shapes >= 1)");
   if (stride < w) return record_msg("ainp_janssen_ola: bad argument (stride >= w)");
-  if (h_max < 1 || h_max > JW_HMAX)
+  if (h_max < 1 || h_max > JN_HMAX)
     return record_msg("ainp_janssen_ola: bad argument (1 <= h_max <= 2048)");
   if ((history != nullptr) != (row_history != nullptr))
     return record_msg("ainp_janssen_ola: bad argument (history needs row_history and the "
                       "reverse)");
-  if (history && (maxit < 1 || maxit > JW_ITMAX || hist_stride < 1 || out_stride < h_max))
+  if (history && (maxit < 1 || maxit > JN_ITMAX || hist_stride < 1 || out_stride < h_max))
     return record_msg("ainp_janssen_ola: bad argument (1 <= maxit <= 1000, hist_stride >= 1, "
                       "out_stride >= h_max)");
   if (n_gaps > 0x7fffffff || n_rows > 0x7fffffff)

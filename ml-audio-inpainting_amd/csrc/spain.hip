@@ -57,12 +57,12 @@
 #include <algorithm>
 #include <cmath>
 
+#include "ar_limits.h"
 #include "common.h"
 
 namespace ainp {
 
 constexpr int SP_WMIN = 8, SP_WMAX = 4096, SP_MMAX = 8192;
-constexpr int SP_HMAX = 2048;   // janssen_windows.hip JW_HMAX
 // Per lane: EPL spectrum slots, 2 EPL time-domain sample pairs, and NK = 2 EPL
 // + 1 half-spectrum bins to rank (template parameters of what follows).
 constexpr int SP_NMAX_256 = 1024;   // the longest transform the 256-lane kernel takes (EPL 2)
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(NT) void spain_kernel(
   const int gs = gap_start[row], gl = gap_len[row];
   double* hrow = obj_history ? obj_history + row * maxit : nullptr;
   // a row whose run does not lie in the window is left alone
-  if (gs < 0 || gl < 1 || gl > SP_HMAX || (int64_t)gs + gl > w) {
+  if (gs < 0 || gl < 1 || gl > JN_HMAX || (int64_t)gs + gl > w) {
     if (tid == 0) iters[row] = 0;
     if (hrow)
       for (int i = tid; i < maxit; i += NT) hrow[i] = NAN;

@@ -20,7 +20,9 @@
 #include <torch/library.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <optional>
+#include <utility>
 #include <vector>
 
 #include "ainp.h"
@@ -211,6 +213,27 @@ void mel_inverse(const Tensor& pinv, const Tensor& mel, int64_t flags, const Ten
 }
 
 // ---------------------------------------------------------------- Janssen
+// the per-row int32 tables of a launch over the rows of `sol`: n elements each,
+// on sol's device; returns their pointers in the order given
+struct RowTable {
+  const Tensor& t;
+  const char* name;
+};
+std::vector<int32_t*> row_tables(const Tensor& sol, int64_t n,
+                                 std::initializer_list<RowTable> tabs) {
+  for (const RowTable& r : tabs) numel_is(r.t, n, r.name);
+  for (const RowTable& r : tabs) same_device(sol, r.t);
+  std::vector<int32_t*> p;
+  for (const RowTable& r : tabs) p.push_back(dev<int32_t>(r.t, r.name, at::kInt));
+  return p;
+}
+// the optional byte workspace of a launch on sol's device -> (pointer, bytes)
+std::pair<uint8_t*, size_t> byte_workspace(const Tensor& sol, const OptT& workspace) {
+  uint8_t* ws = opt<uint8_t>(workspace, "workspace", at::kByte);
+  if (ws) same_device(sol, *workspace);
+  return {ws, ws ? (size_t)workspace->numel() : 0};
+}
+
 void janssen(const Tensor& sol, const Tensor& n, const Tensor& gap_start, const Tensor& gap_len,
              int64_t p, int64_t maxit, const OptT& history, const Tensor& iters_done,
              const OptT& workspace, int64_t method) {
@@ -220,14 +243,8 @@ void janssen(const Tensor& sol, const Tensor& n, const Tensor& gap_start, const 
               "method must be 0 (lpc) or 1 (arburg)");
   const int64_t n_seg = sol.size(0);
   double* x = dev<double>(sol, "sol", at::kDouble);
-  numel_is(n, n_seg, "n");
-  numel_is(gap_start, n_seg, "gap_start");
-  numel_is(gap_len, n_seg, "gap_len");
-  numel_is(iters_done, n_seg, "iters_done");
-  same_device(sol, n);
-  same_device(sol, gap_start);
-  same_device(sol, gap_len);
-  same_device(sol, iters_done);
+  const auto tab = row_tables(sol, n_seg, {{n, "n"}, {gap_start, "gap_start"},
+                                           {gap_len, "gap_len"}, {iters_done, "iters_done"}});
   TORCH_CHECK(p >= 1 && p <= INT32_MAX && maxit >= 1 && maxit <= INT32_MAX,
               "p and maxit must be positive");
   double* h = opt<double>(history, "history", at::kDouble);
@@ -236,13 +253,9 @@ void janssen(const Tensor& sol, const Tensor& n, const Tensor& gap_start, const 
     TORCH_CHECK(history->dim() == 3 && history->size(0) == n_seg && history->size(1) == maxit,
                 "history must be [n_segments, maxit, max gap_len], got ", history->sizes());
   }
-  uint8_t* ws = opt<uint8_t>(workspace, "workspace", at::kByte);
-  if (ws) same_device(sol, *workspace);
-  chk(ainp_janssen_ex(x, n_seg, sol.size(1), dev<int32_t>(n, "n", at::kInt),
-                      dev<int32_t>(gap_start, "gap_start", at::kInt),
-                      dev<int32_t>(gap_len, "gap_len", at::kInt), (int)p, (int)maxit, h,
-                      dev<int32_t>(iters_done, "iters_done", at::kInt), ws,
-                      ws ? (size_t)workspace->numel() : 0, (int)method, stream_of(sol)),
+  const auto [ws, ws_bytes] = byte_workspace(sol, workspace);
+  chk(ainp_janssen_ex(x, n_seg, sol.size(1), tab[0], tab[1], tab[2], (int)p, (int)maxit, h,
+                      tab[3], ws, ws_bytes, (int)method, stream_of(sol)),
       "janssen");
 }
 
@@ -255,22 +268,12 @@ void ar_extrapolate(const Tensor& sol, const Tensor& n, const Tensor& gap_start,
               "method must be 0 (lpc) or 1 (arburg)");
   const int64_t n_seg = sol.size(0);
   double* x = dev<double>(sol, "sol", at::kDouble);
-  numel_is(n, n_seg, "n");
-  numel_is(gap_start, n_seg, "gap_start");
-  numel_is(gap_len, n_seg, "gap_len");
-  numel_is(status, n_seg, "status");
-  same_device(sol, n);
-  same_device(sol, gap_start);
-  same_device(sol, gap_len);
-  same_device(sol, status);
+  const auto tab = row_tables(sol, n_seg, {{n, "n"}, {gap_start, "gap_start"},
+                                           {gap_len, "gap_len"}, {status, "status"}});
   TORCH_CHECK(p >= 1 && p <= INT32_MAX && w >= 1 && w <= INT32_MAX, "p and w must be positive");
-  uint8_t* ws = opt<uint8_t>(workspace, "workspace", at::kByte);
-  if (ws) same_device(sol, *workspace);
-  chk(ainp_ar_extrapolate(x, n_seg, sol.size(1), dev<int32_t>(n, "n", at::kInt),
-                          dev<int32_t>(gap_start, "gap_start", at::kInt),
-                          dev<int32_t>(gap_len, "gap_len", at::kInt), (int)p, (int)w, (int)method,
-                          dev<int32_t>(status, "status", at::kInt), ws,
-                          ws ? (size_t)workspace->numel() : 0, stream_of(sol)),
+  const auto [ws, ws_bytes] = byte_workspace(sol, workspace);
+  chk(ainp_ar_extrapolate(x, n_seg, sol.size(1), tab[0], tab[1], tab[2], (int)p, (int)w,
+                          (int)method, tab[3], ws, ws_bytes, stream_of(sol)),
       "ar_extrapolate");
 }
 
@@ -360,12 +363,8 @@ void spain(const Tensor& sol, const Tensor& gap_start, const Tensor& gap_len, in
   TORCH_CHECK(algorithm == AINP_SPAIN_A || algorithm == AINP_SPAIN_S,
               "algorithm must be 0 (aspain) or 1 (sspain)");
   const int64_t n_rows = sol.size(0), w = sol.size(1);
-  numel_is(gap_start, n_rows, "gap_start");
-  numel_is(gap_len, n_rows, "gap_len");
-  numel_is(iters, n_rows, "iters");
-  same_device(sol, gap_start);
-  same_device(sol, gap_len);
-  same_device(sol, iters);
+  const auto tab = row_tables(sol, n_rows, {{gap_start, "gap_start"}, {gap_len, "gap_len"},
+                                            {iters, "iters"}});
   TORCH_CHECK(w <= INT32_MAX && red >= 1 && red <= INT32_MAX && s >= 1 && s <= INT32_MAX &&
                   r >= 1 && r <= INT32_MAX && maxit >= 1 && maxit <= INT32_MAX,
               "red, s, r and maxit must be positive");
@@ -376,13 +375,10 @@ void spain(const Tensor& sol, const Tensor& gap_start, const Tensor& gap_len, in
                     obj_history->size(1) == maxit,
                 "obj_history must be [n_rows, maxit], got ", obj_history->sizes());
   }
-  uint8_t* ws = opt<uint8_t>(workspace, "workspace", at::kByte);
-  if (ws) same_device(sol, *workspace);
-  chk(ainp_spain(dev<double>(sol, "sol", at::kDouble), n_rows, w,
-                 dev<int32_t>(gap_start, "gap_start", at::kInt),
-                 dev<int32_t>(gap_len, "gap_len", at::kInt), (int)w, (int)red, (int)algorithm,
-                 (int)s, (int)r, epsilon, (int)maxit, dev<int32_t>(iters, "iters", at::kInt), h, ws,
-                 ws ? (size_t)workspace->numel() : 0, stream_of(sol)),
+  const auto [ws, ws_bytes] = byte_workspace(sol, workspace);
+  chk(ainp_spain(dev<double>(sol, "sol", at::kDouble), n_rows, w, tab[0], tab[1], (int)w,
+                 (int)red, (int)algorithm, (int)s, (int)r, epsilon, (int)maxit, tab[2], h, ws,
+                 ws_bytes, stream_of(sol)),
       "spain");
 }
 

@@ -160,14 +160,11 @@ def run_evaluation(input_dir, output_dir, model_type, checkpoint, config_path):
     return outs
 
 
-def run_janssen_evaluation(input_dir, output_dir, p=512, w=4096, maxit=20):
-    """The AR baseline on the clips and the gap of inpaint(): every .flac of
-    input_dir gets the 80 ms gap at 2.0 s, all gaps are filled in one batch by
-    the Janssen algorithm in the time domain, and each result is written as
-    <stem>_janssen_inpainted.flac.  Returns {filename: gap SDR in dB}
-    (models/AudioReg/model_eval.m:60), measured before save_audio's
-    normalisation and 16-bit quantisation."""
-    from models.AudioReg import gap_sdr, janssen_inpaint
+def _evaluate_gap_filler(input_dir, output_dir, suffix, fill):
+    """What the signal-processing rows share: the clips with their gap go to
+    fill(clean, masks) -> restored as one batch, the results to
+    <stem>_<suffix>_inpainted.flac, the gap SDRs to the caller."""
+    from models.AudioReg import gap_sdr
     if not os.path.isdir(input_dir):
         print(f"Error: Input directory not found: {input_dir}")
         return
@@ -183,13 +180,21 @@ def run_janssen_evaluation(input_dir, output_dir, p=512, w=4096, maxit=20):
         clean.append(audio.astype(np.float64))
         masks.append(mask_td > 0)
         srs.append(sr)
-    restored = janssen_inpaint(clean, masks, p=p, w=w, maxit=maxit) if clean else []
+    restored = fill(clean, masks) if clean else []
     sdrs = {}
     for filename, x, y, m, sr in zip(flac_files, clean, restored, masks, srs):
-        out = os.path.join(output_dir, f"{os.path.splitext(filename)[0]}_janssen_inpainted.flac")
+        out = os.path.join(output_dir, f"{os.path.splitext(filename)[0]}_{suffix}_inpainted.flac")
         utils.save_audio(y, file_path=out, sample_rate=sr)
         sdrs[filename] = gap_sdr(x, y, m)
     return sdrs
+
+
+def run_janssen_evaluation(input_dir, output_dir, p=512, w=4096, maxit=20):
+    """The AR baseline on the clips and the gap of inpaint(): run_ar_evaluation's
+    "janssen" cell with the "lpc" estimator, written as <stem>_janssen_inpainted.flac.
+    Returns {filename: gap SDR in dB} (models/AudioReg/model_eval.m:60)."""
+    return run_ar_evaluation(input_dir, output_dir, algorithm="janssen", method="lpc", p=p, w=w,
+                             maxit=maxit)
 
 
 AR_ALGORITHMS = ("extrapolation", "janssen", "janssen_hann", "janssen_rect", "janssen_tukey")
@@ -206,41 +211,21 @@ def run_ar_evaluation(input_dir, output_dir, algorithm="janssen", method="lpc", 
     <stem>_<algorithm>[_arburg]_inpainted.flac.  Returns {filename: gap SDR in
     dB}, measured before save_audio's normalisation and 16-bit quantisation.
     maxit does not apply to "extrapolation"."""
-    from models.AudioReg import ar_extrapolate, gap_sdr, janssen_inpaint, janssen_windowed
+    from models.AudioReg import ar_extrapolate, janssen_inpaint, janssen_windowed
     from ainp.janssen import method_id
     if algorithm not in AR_ALGORITHMS:
         raise ValueError(f"algorithm must be one of {AR_ALGORITHMS}, got {algorithm!r}")
     suffix = algorithm + ("_arburg" if method_id(method) else "")
-    if not os.path.isdir(input_dir):
-        print(f"Error: Input directory not found: {input_dir}")
-        return
-    os.makedirs(output_dir, exist_ok=True)
-    if not torch.cuda.is_available():
-        raise RuntimeError("model_eval runs on the MI355X kernels: no GPU visible")
-    flac_files = sorted(f for f in os.listdir(input_dir) if f.lower().endswith(".flac"))
-    print(f"Found {len(flac_files)} .flac files in {input_dir}")
-    clean, masks, srs = [], [], []
-    for filename in flac_files:
-        audio, sr = utils.load_audio(os.path.join(input_dir, filename))
-        mask_td, _ = utils.create_gap_mask(len(audio), GAP_LEN_S, sr, gap_start_s=GAP_START_S)
-        clean.append(audio.astype(np.float64))
-        masks.append(mask_td > 0)
-        srs.append(sr)
-    if not clean:
-        restored = []
-    elif algorithm == "janssen":
-        restored = janssen_inpaint(clean, masks, p=p, w=w, maxit=maxit, method=method)
-    elif algorithm.startswith("janssen_"):
-        restored = janssen_windowed(clean, masks, p=p, w=w, a=a, wtype=algorithm[len("janssen_"):],
-                                    maxit=maxit, method=method)
-    else:
-        restored = ar_extrapolate(clean, masks, p=p, w=w, method=method)
-    sdrs = {}
-    for filename, x, y, m, sr in zip(flac_files, clean, restored, masks, srs):
-        out = os.path.join(output_dir, f"{os.path.splitext(filename)[0]}_{suffix}_inpainted.flac")
-        utils.save_audio(y, file_path=out, sample_rate=sr)
-        sdrs[filename] = gap_sdr(x, y, m)
-    return sdrs
+
+    def fill(clean, masks):
+        if algorithm == "janssen":
+            return janssen_inpaint(clean, masks, p=p, w=w, maxit=maxit, method=method)
+        if algorithm.startswith("janssen_"):
+            return janssen_windowed(clean, masks, p=p, w=w, a=a, maxit=maxit, method=method,
+                                    wtype=algorithm[len("janssen_"):])
+        return ar_extrapolate(clean, masks, p=p, w=w, method=method)
+
+    return _evaluate_gap_filler(input_dir, output_dir, suffix, fill)
 
 
 SPAIN_ALGORITHMS = ("aspain", "sspain")
@@ -254,32 +239,12 @@ def run_spain_evaluation(input_dir, output_dir, algorithm="aspain", w=4096, a=10
     gaps are filled in one batch, and each result is written as
     <stem>_<algorithm>_inpainted.flac.  Returns {filename: gap SDR in dB},
     measured before save_audio's normalisation and 16-bit quantisation."""
-    from models.AudioReg import gap_sdr, spain_inpaint
+    from models.AudioReg import spain_inpaint
     if algorithm not in SPAIN_ALGORITHMS:
         raise ValueError(f"algorithm must be one of {SPAIN_ALGORITHMS}, got {algorithm!r}")
-    if not os.path.isdir(input_dir):
-        print(f"Error: Input directory not found: {input_dir}")
-        return
-    os.makedirs(output_dir, exist_ok=True)
-    if not torch.cuda.is_available():
-        raise RuntimeError("model_eval runs on the MI355X kernels: no GPU visible")
-    flac_files = sorted(f for f in os.listdir(input_dir) if f.lower().endswith(".flac"))
-    print(f"Found {len(flac_files)} .flac files in {input_dir}")
-    clean, masks, srs = [], [], []
-    for filename in flac_files:
-        audio, sr = utils.load_audio(os.path.join(input_dir, filename))
-        mask_td, _ = utils.create_gap_mask(len(audio), GAP_LEN_S, sr, gap_start_s=GAP_START_S)
-        clean.append(audio.astype(np.float64))
-        masks.append(mask_td > 0)
-        srs.append(sr)
-    restored = spain_inpaint(clean, masks, algorithm=algorithm, w=w, a=a, **solver) if clean else []
-    sdrs = {}
-    for filename, x, y, m, sr in zip(flac_files, clean, restored, masks, srs):
-        out = os.path.join(output_dir,
-                           f"{os.path.splitext(filename)[0]}_{algorithm}_inpainted.flac")
-        utils.save_audio(y, file_path=out, sample_rate=sr)
-        sdrs[filename] = gap_sdr(x, y, m)
-    return sdrs
+    return _evaluate_gap_filler(
+        input_dir, output_dir, algorithm,
+        lambda clean, masks: spain_inpaint(clean, masks, algorithm=algorithm, w=w, a=a, **solver))
 
 
 if __name__ == "__main__":

@@ -8,13 +8,18 @@ parity test uses, what two independent float64 solvers differ by and what
 rounding the input to float32 moves; DESIGN §14 records the figures.
 """
 import ctypes
+import importlib.util
 import inspect
+import json
+import os
 
 import numpy as np
 import pytest
 
 import janssen_ref as R
 import janssen_windowed_ref as W
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 # the known answers of the support: (w, a, [s0, e0)) -> 0-based [lo, hi)
 SUPPORTS = [((256, 64, 900, 980), (652, 1228)),
@@ -156,6 +161,36 @@ def test_refusals():
     # the windows that hold the gap reach [652, 1228): a neighbour from 1484 on, whose own
     # windows start at 1229, is no obstacle
     assert len(plan_windows([_mask(2000, (900, 980), (1484, 1490))], p=32, w=256, a=64)) == 6 + 4
+
+
+def _plan_gen():
+    spec = importlib.util.spec_from_file_location(
+        "gen_window_plans", os.path.join(GOLDEN, "gen_window_plans.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+plan_gen = _plan_gen()
+
+
+@pytest.fixture(scope="module")
+def golden_plans():
+    with open(os.path.join(GOLDEN, "window_plans.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(plan_gen.CASES)
+    return want
+
+
+@pytest.mark.parametrize("name", list(plan_gen.CASES))
+def test_plans_unchanged(name, golden_plans):
+    """plan_segments, plan_windows and plan_spain_windows give the tables -- every
+    field's values, dtype and shape -- or the ValueError text that the package
+    gave before the planners shared one row loop (tests/golden/window_plans.json)."""
+    got = plan_gen.run_case(name)
+    assert sorted(got) == sorted(golden_plans[name])
+    for field, want in golden_plans[name].items():
+        assert got[field] == want, (name, field)
 
 
 def test_model_eval_refuses_unknown_algorithms(tmp_path):
