@@ -346,6 +346,52 @@ int ainp_spain(double* sol, int64_t n_rows, int64_t stride, const int32_t* gap_s
                size_t ws_bytes, void* stream);
 size_t ainp_spain_workspace(int64_t n_rows, int w, int red, int algorithm);
 
+/* SPAIN over whole signals with a Gabor frame and an optional unitary
+ * "sparsity-enhancing" basis (references/basisopt/a_spain_learned.m,
+ * s_spain_learned.m, hard_thresholding_dgtreal.m; csrc/spain_learned.hip;
+ * DESIGN 14.2).  Float64.  x [n_signals][L]: independent problems of one length
+ * L, observed [n_signals][L] nonzero where a sample is reliable (missing samples
+ * are read as zeros; any number of gaps).  With K = M/2 + 1, N = L/a, g the
+ * periodic Hann window of length w, gd[i] = g[i] / (M sum_j g^2[(i mod a) + j a])
+ * and idx(n, i) = (n a - w/2 + i) mod L:
+ *   dgt(x, win): column n = the first K bins of FFT_M of the zero buffer with
+ *     x[idx(n, i)] win[i] at (i - w/2) mod M;
+ *   idgt(c, win): per column irfft_M(c) M (imaginary parts of rows 0 and K-1
+ *     ignored), entries (i - w/2) mod M times win[i] added to x[idx(n, i)].
+ * basis (nullable) [K][K] row-major, re / im interleaved: the unitary U applied
+ * to every column; NULL is U = I.  H_k keeps, per column, the k largest
+ * magnitudes with rows 0 and K-1 ranked by |z| / sqrt 2 (equal ones: the lower
+ * row first; everything if k >= K).  proj puts the observed samples back.  With
+ * x = the input, k = s, cnt = 1, while cnt <= maxit:
+ *   AINP_SPAIN_A (z = U dgt(x, g), u = 0 of K x N):
+ *     zb = H_k(z + u);  obj = |z - zb|_F over the K x N half spectrum;
+ *     [record, stop];  x = proj(idgt(U^H (zb - u), gd));  z = U dgt(x, g);
+ *     u += z - zb
+ *   AINP_SPAIN_S (u = 0 of L samples):
+ *     zb = H_k(U dgt(x - u, gd));  xe = idgt(U^H zb, g);  obj = |xe - x|_2;
+ *     [record, stop];  x = proj(xe + u);  u += xe - x
+ *   then cnt += 1, and k += s if cnt mod r == 0.
+ * [record, stop] as ainp_spain's, per signal.  On return only the missing
+ * samples of x are written.  iters int32 [n_signals]; obj_history (nullable)
+ * [n_signals][maxit], NaN after a signal's last pass.  A pass is a sequence of
+ * launches (no cooperative launch); every stop is decided on the device, once,
+ * from sums added in a fixed order, no float atomics: the same bits on every
+ * call.  The host reads the per-signal stop flags every 32 passes (a stream
+ * synchronisation) only to stop issuing launches; the environment variable
+ * AINP_SPAIN_LEARNED_CHUNK sets another interval (0: never), which changes no
+ * result.
+ * Supported: M a power of two, 8 <= M <= 2048; w a power of two, 8 <= w <= M;
+ * a divides w, w / a >= 2; L a positive multiple of M with L <= 2^22 (the frame
+ * cap: L / a <= 2^22 / a); s, r >= 1; epsilon >= 0; 1 <= maxit <= 65536.
+ * Anything else is AINP_EINVAL without a launch.  workspace: 16-byte aligned,
+ * at least ainp_spain_learned_workspace(...) bytes (0 for a bad shape). */
+int ainp_spain_learned(double* x, const uint8_t* observed, int64_t L, int64_t n_signals, int w,
+                       int a, int M, const double* basis, int algorithm, int s, int r,
+                       double epsilon, int maxit, int32_t* iters, double* obj_history,
+                       void* workspace, size_t ws_bytes, void* stream);
+size_t ainp_spain_learned_workspace(int64_t L, int64_t n_signals, int w, int a, int M,
+                                    int has_basis, int algorithm);
+
 /* ------------------------------------------------------------------------ */
 /* fp32 GEMM on MFMA (fp32-accurate bf16 split by default, exact f32 on flag) */
 /* ------------------------------------------------------------------------ */

@@ -2325,3 +2325,40 @@ def spain(sol, gap_start, gap_len, algorithm="aspain", red=2, s=1, r=1, epsilon=
         _T.spain(sol, _dev_i32(gs, dv), _dev_i32(gl, dv), int(red), alg, int(s), int(r),
                  float(epsilon), maxit, iters, hist, ws)
     return iters, hist
+
+
+def spain_learned(x, observed, basis=None, algorithm="aspain", w=1024, a=256, M=None, s=1, r=1,
+                  epsilon=0.1, maxit=None, return_history=False):
+    """ainp_spain_learned: A-SPAIN or S-SPAIN over whole signals with a Gabor
+    frame and an optional unitary basis, float64.  x [n_signals, L] float64 cuda,
+    L a multiple of M, updated in place on the missing samples only; observed
+    [n_signals, L] uint8 cuda, nonzero where a sample is reliable.  basis: None
+    or [K, K, 2] float64 cuda (re, im), K = M / 2 + 1; its unitarity is the
+    caller's to check (ainp.spain_learned.check_basis).  M None: 2 w; maxit None:
+    ceil(K r / s).  Returns (iters int32 [n_signals], objective [n_signals,
+    maxit] float64 or None; NaN after a signal's last pass)."""
+    from . import spain_learned as _sl
+    _req(x, "x", dtype=torch.float64)
+    _req(observed, "observed", dtype=torch.uint8)
+    alg = _sp.algorithm_id(algorithm)
+    w, a, M, maxit = _sl.check_args(w, a, M, s, r, epsilon, maxit)
+    if x.dim() != 2 or observed.shape != x.shape:
+        raise ValueError("x and observed must both be [n_signals, L]")
+    nsig, L = x.shape
+    if L < M or L % M or L > _sl.L_MAX:
+        raise ValueError(f"L must be a multiple of M = {M} in [M, {_sl.L_MAX}], got L = {L}")
+    K = M // 2 + 1
+    if basis is not None:
+        _req(basis, "basis", dtype=torch.float64)
+        if tuple(basis.shape) != (K, K, 2):
+            raise ValueError(f"basis must be [K, K, 2] with K = M / 2 + 1 = {K}, "
+                             f"got {tuple(basis.shape)}")
+    dv = x.device
+    iters, hist, ws = _row_outputs(
+        dv, nsig, (nsig, maxit) if return_history else None,
+        _lib.lib.ainp_spain_learned_workspace(L, nsig, w, a, M, int(basis is not None), alg)
+        if nsig else 0)
+    if nsig:
+        _T.spain_learned(x, observed, w, a, M, basis, alg, int(s), int(r), float(epsilon), maxit,
+                         iters, hist, ws)
+    return iters, hist

@@ -382,6 +382,47 @@ void spain(const Tensor& sol, const Tensor& gap_start, const Tensor& gap_len, in
       "spain");
 }
 
+// SPAIN over whole signals with a Gabor frame and an optional unitary basis
+void spain_learned(const Tensor& x, const Tensor& observed, int64_t w, int64_t a, int64_t M,
+                   const OptT& basis, int64_t algorithm, int64_t s, int64_t r, double epsilon,
+                   int64_t maxit, const Tensor& iters, const OptT& obj_history,
+                   const OptT& workspace) {
+  GUARD(x);
+  TORCH_CHECK(x.dim() == 2, "x must be [n_signals, L]");
+  TORCH_CHECK(algorithm == AINP_SPAIN_A || algorithm == AINP_SPAIN_S,
+              "algorithm must be 0 (aspain) or 1 (sspain)");
+  const int64_t n_sig = x.size(0), L = x.size(1);
+  TORCH_CHECK(observed.dim() == 2 && observed.size(0) == n_sig && observed.size(1) == L,
+              "observed must be [n_signals, L] as x, got ", observed.sizes());
+  numel_is(iters, n_sig, "iters");
+  same_device(x, observed);
+  same_device(x, iters);
+  TORCH_CHECK(w >= 1 && w <= INT32_MAX && a >= 1 && a <= INT32_MAX && M >= 2 && M <= INT32_MAX &&
+                  s >= 1 && s <= INT32_MAX && r >= 1 && r <= INT32_MAX && maxit >= 1 &&
+                  maxit <= INT32_MAX,
+              "w, a, M, s, r and maxit must be positive");
+  const double* u = opt<double>(basis, "basis", at::kDouble);
+  if (u) {
+    same_device(x, *basis);
+    TORCH_CHECK(basis->dim() == 3 && basis->size(0) == M / 2 + 1 && basis->size(1) == M / 2 + 1 &&
+                    basis->size(2) == 2,
+                "basis must be [M / 2 + 1, M / 2 + 1, 2] (re, im), got ", basis->sizes());
+  }
+  double* h = opt<double>(obj_history, "obj_history", at::kDouble);
+  if (h) {
+    same_device(x, *obj_history);
+    TORCH_CHECK(obj_history->dim() == 2 && obj_history->size(0) == n_sig &&
+                    obj_history->size(1) == maxit,
+                "obj_history must be [n_signals, maxit], got ", obj_history->sizes());
+  }
+  const auto [ws, ws_bytes] = byte_workspace(x, workspace);
+  chk(ainp_spain_learned(dev<double>(x, "x", at::kDouble),
+                         dev<uint8_t>(observed, "observed", at::kByte), L, n_sig, (int)w, (int)a,
+                         (int)M, u, (int)algorithm, (int)s, (int)r, epsilon, (int)maxit,
+                         dev<int32_t>(iters, "iters", at::kInt), h, ws, ws_bytes, stream_of(x)),
+      "spain_learned");
+}
+
 // ------------------------------------------------------------------- GEMM
 void gemm(int64_t M, int64_t N, int64_t K, double alpha, at::TensorList A, int64_t sam,
           int64_t sak, int64_t strideA, at::TensorList B, int64_t sbk, int64_t sbn,
@@ -2020,6 +2061,9 @@ TORCH_LIBRARY(ainp, m) {
   m.def("spain(Tensor(a!) sol, Tensor gap_start, Tensor gap_len, int red, int algorithm, int s, "
         "int r, float epsilon, int maxit, Tensor(b!) iters, Tensor(c!)? obj_history, "
         "Tensor? workspace) -> ()");
+  m.def("spain_learned(Tensor(a!) x, Tensor observed, int w, int a, int M, Tensor? basis, "
+        "int algorithm, int s, int r, float epsilon, int maxit, Tensor(b!) iters, "
+        "Tensor(c!)? obj_history, Tensor? workspace) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
@@ -2111,6 +2155,7 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("janssen_windows", &janssen_windows);
   m.impl("janssen_ola", &janssen_ola);
   m.impl("spain", &spain);
+  m.impl("spain_learned", &spain_learned);
 }
 
 // The ops write through raw device pointers like the C ABI; autograd is the
@@ -2205,4 +2250,5 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("janssen_windows", torch::CppFunction::makeFallthrough());
   m.impl("janssen_ola", torch::CppFunction::makeFallthrough());
   m.impl("spain", torch::CppFunction::makeFallthrough());
+  m.impl("spain_learned", torch::CppFunction::makeFallthrough());
 }

@@ -247,6 +247,25 @@ def run_spain_evaluation(input_dir, output_dir, algorithm="aspain", w=4096, a=10
         lambda clean, masks: spain_inpaint(clean, masks, algorithm=algorithm, w=w, a=a, **solver))
 
 
+def run_spain_learned_evaluation(input_dir, output_dir, basis=None, algorithm="aspain", w=1024,
+                                 a=256, **solver):
+    """SPAIN over the whole signal (references/basisopt: a_spain_learned.m /
+    s_spain_learned.m) on the clips and the gap of inpaint(): algorithm "aspain"
+    or "sspain", the Gabor frame of a Hann window of w samples every a samples,
+    basis None (the global SPAIN row) or a unitary [K, K] matrix (the learned
+    row), **solver handed to spain_learned_inpaint (M, s, r, epsilon, maxit).
+    Each result is written as <stem>_<algorithm>_global_inpainted.flac without a
+    basis and <stem>_<algorithm>_learned_inpainted.flac with one.  Returns
+    {filename: gap SDR in dB}, measured as run_spain_evaluation measures it."""
+    from models.AudioReg import spain_learned_inpaint
+    if algorithm not in SPAIN_ALGORITHMS:
+        raise ValueError(f"algorithm must be one of {SPAIN_ALGORITHMS}, got {algorithm!r}")
+    return _evaluate_gap_filler(
+        input_dir, output_dir, f"{algorithm}_{'global' if basis is None else 'learned'}",
+        lambda clean, masks: spain_learned_inpaint(clean, masks, basis=basis, algorithm=algorithm,
+                                                   w=w, a=a, **solver))
+
+
 if __name__ == "__main__":
     # model_eval.py:229-256 (CNN-LSTM configuration by default)
     run_evaluation(input_dir=sys.argv[1] if len(sys.argv) > 1 else "../test_samples",
