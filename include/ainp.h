@@ -346,6 +346,33 @@ int ainp_spain(double* sol, int64_t n_rows, int64_t stride, const int32_t* gap_s
                size_t ws_bytes, void* stream);
 size_t ainp_spain_workspace(int64_t n_rows, int w, int red, int algorithm);
 
+/* S-SPAIN with the OMP coefficient update (references/spain/sspain.m with
+ * f_update = 'OMP'; csrc/spain_omp.hip) on the same rows, frame
+ * and layout as ainp_spain.  The loop is AINP_SPAIN_S's with zb = OMP_k(x - u)
+ * in place of H_k(A(x - u)).  With d_m[i] = exp(2 pi i m i / M) / sqrt(M), i <
+ * w, OMP_k(v) returns a conjugate-symmetric z of M coefficients: r = v, S
+ * empty, tol = 10^(errdb / 20) |v|_2; repeat: stop if |r|_2 <= tol; stop if
+ * |S| = k; take the unselected m in [0, M/2] with the largest |(A r)_m| (plain
+ * magnitudes, equal ones: the lower m); stop if its real unknowns (one for m =
+ * 0 and m = M/2, else two) would bring the total above w; stop if a new real
+ * column's squared norm orthogonal to the chosen columns is under 1e-10 of its
+ * squared norm; else add m to S, z = argmin |v - A* z|_2 over conjugate-
+ * symmetric z on S and its mirror (real at DC and Nyquist), r = v - A* z.
+ * n_atoms (nullable) int32 [n_rows][maxit]: |S| at the end of each evaluated
+ * pass, -1 after the last.  iters, obj_history, the record, the stop, the k
+ * schedule k(cnt) = s (1 + cnt / r - 1 / r) (integer divisions), rows left alone
+ * and determinism as ainp_spain's.
+ * Supported: ainp_spain's range, and -300 <= errdb <= 0, and min(2 k(maxit), w)
+ * <= 512 real unknowns (every w <= 512; k(maxit) <= 256 above).  Anything else
+ * is AINP_EINVAL naming the rule, without a launch.  workspace: at least
+ * ainp_spain_omp_workspace(...) bytes (a row's inverse Cholesky factor, D (D +
+ * 1) / 2 doubles with D = min(w, 512); 0 for a bad shape). */
+int ainp_spain_omp(double* sol, int64_t n_rows, int64_t stride, const int32_t* gap_start,
+                   const int32_t* gap_len, int w, int red, int s, int r, double epsilon,
+                   int maxit, double errdb, int32_t* iters, double* obj_history,
+                   int32_t* n_atoms, void* workspace, size_t ws_bytes, void* stream);
+size_t ainp_spain_omp_workspace(int64_t n_rows, int w, int red);
+
 /* SPAIN over whole signals with a Gabor frame and an optional unitary
  * "sparsity-enhancing" basis (references/basisopt/a_spain_learned.m,
  * s_spain_learned.m, hard_thresholding_dgtreal.m; csrc/spain_learned.hip;

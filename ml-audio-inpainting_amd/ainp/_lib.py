@@ -269,6 +269,10 @@ _SIGS = {
     "ainp_spain": (c_int, [P, c_int64, c_int64, P, P, c_int, c_int, c_int, c_int, c_int, c_double,
                            c_int, P, P, P, c_size_t, P]),
     "ainp_spain_workspace": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    # S-SPAIN with the OMP coefficient update (csrc/spain_omp.hip)
+    "ainp_spain_omp": (c_int, [P, c_int64, c_int64, P, P, c_int, c_int, c_int, c_int, c_double,
+                               c_int, c_double, P, P, P, P, c_size_t, P]),
+    "ainp_spain_omp_workspace": (c_size_t, [c_int64, c_int, c_int]),
     # A-SPAIN / S-SPAIN over the whole signal with a unitary basis (csrc/spain_learned.hip)
     "ainp_spain_learned": (c_int, [P, P, c_int64, c_int64, c_int, c_int, c_int, P, c_int, c_int,
                                    c_int, c_double, c_int, P, P, P, c_size_t, P]),

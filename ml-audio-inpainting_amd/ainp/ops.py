@@ -2327,6 +2327,36 @@ def spain(sol, gap_start, gap_len, algorithm="aspain", red=2, s=1, r=1, epsilon=
     return iters, hist
 
 
+def spain_omp(sol, gap_start, gap_len, red=2, s=1, r=1, epsilon=0.1, maxit=None, errdb=-40.0,
+              return_history=False):
+    """ainp_spain_omp: S-SPAIN with the OMP coefficient update on a batch of
+    windows, float64, one workgroup per row; sol, gap_start, gap_len and the
+    in-place result as spain's.  errdb: OMP's target residual in dB relative to
+    the block it approximates.  maxit None: spain's default, clipped so that the
+    cap on the least squares' real unknowns holds.  Returns (iters int32
+    [n_rows], objective [n_rows, maxit] float64 or None, atoms [n_rows, maxit]
+    int32 or None: the atoms chosen in every pass, -1 after a row's last)."""
+    _req(sol, "sol", dtype=torch.float64)
+    if sol.dim() != 2:
+        raise ValueError("sol must be [n_rows, w]")
+    nrows, w = sol.shape
+    maxit = _sp.check_omp_args(w, red, s, r, epsilon, maxit, errdb)
+    gs = np.asarray(gap_start, dtype=np.int64).reshape(-1)
+    gl = np.asarray(gap_len, dtype=np.int64).reshape(-1)
+    if gs.size != nrows or gl.size != nrows:
+        raise ValueError("gap_start and gap_len need one entry per row")
+    _check_runs(gs, gl, w, "run must lie inside its window")
+    dv = sol.device
+    iters, hist, ws = _row_outputs(dv, nrows, (nrows, maxit) if return_history else None,
+                                   _lib.lib.ainp_spain_omp_workspace(nrows, int(w), int(red)))
+    atoms = (torch.full((nrows, maxit), -1, device=dv, dtype=torch.int32)
+             if return_history else None)
+    if nrows:
+        _T.spain_omp(sol, _dev_i32(gs, dv), _dev_i32(gl, dv), int(red), int(s), int(r),
+                     float(epsilon), maxit, float(errdb), iters, hist, atoms, ws)
+    return iters, hist, atoms
+
+
 def spain_learned(x, observed, basis=None, algorithm="aspain", w=1024, a=256, M=None, s=1, r=1,
                   epsilon=0.1, maxit=None, return_history=False):
     """ainp_spain_learned: A-SPAIN or S-SPAIN over whole signals with a Gabor

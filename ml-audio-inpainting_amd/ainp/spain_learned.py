@@ -6,7 +6,9 @@ One ADMM loop runs over the whole signal with a Gabor frame (periodic Hann
 window of w samples every a samples, M channels) and one stopping rule; the
 coefficients of every frame are rotated by a unitary basis before the hard
 threshold.  Without a basis this is the global, non-segmented SPAIN row.  The
-basis is an input: basis_opt_new.m, which learns it, is not ported.
+basis is an input: basis_opt_new.m, which learns it, is not ported.  (The
+reference's OMP coefficient update exists only in the segment-wise sspain.m:
+ainp.spain.spain_inpaint(f_update="OMP"))
 
 Signals are padded with observed zeros to a multiple of M and grouped by padded
 length; each group is one ainp_spain_learned launch sequence

@@ -10,5 +10,6 @@ constexpr int JN_PMAX = 3072;    // AR order
 constexpr int JN_NMAX = 16384;   // samples of a segment or a window
 constexpr int JN_HMAX = 2048;    // missing samples of a segment, a window or a gap
 constexpr int JN_ITMAX = 1000;   // Janssen iterations
+constexpr int AINP_SPAIN_OMP_DIMS = 512;   // real unknowns of S-SPAIN OMP's least squares
 
 }  // namespace ainp

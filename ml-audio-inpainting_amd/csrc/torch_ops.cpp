@@ -382,6 +382,39 @@ void spain(const Tensor& sol, const Tensor& gap_start, const Tensor& gap_len, in
       "spain");
 }
 
+// S-SPAIN with the OMP coefficient update on the same rows
+void spain_omp(const Tensor& sol, const Tensor& gap_start, const Tensor& gap_len, int64_t red,
+               int64_t s, int64_t r, double epsilon, int64_t maxit, double errdb,
+               const Tensor& iters, const OptT& obj_history, const OptT& n_atoms,
+               const OptT& workspace) {
+  GUARD(sol);
+  TORCH_CHECK(sol.dim() == 2, "sol must be [n_rows, w]");
+  const int64_t n_rows = sol.size(0), w = sol.size(1);
+  const auto tab = row_tables(sol, n_rows, {{gap_start, "gap_start"}, {gap_len, "gap_len"},
+                                            {iters, "iters"}});
+  TORCH_CHECK(w <= INT32_MAX && red >= 1 && red <= INT32_MAX && s >= 1 && s <= INT32_MAX &&
+                  r >= 1 && r <= INT32_MAX && maxit >= 1 && maxit <= INT32_MAX,
+              "red, s, r and maxit must be positive");
+  double* h = opt<double>(obj_history, "obj_history", at::kDouble);
+  if (h) {
+    same_device(sol, *obj_history);
+    TORCH_CHECK(obj_history->dim() == 2 && obj_history->size(0) == n_rows &&
+                    obj_history->size(1) == maxit,
+                "obj_history must be [n_rows, maxit], got ", obj_history->sizes());
+  }
+  int32_t* na = opt<int32_t>(n_atoms, "n_atoms", at::kInt);
+  if (na) {
+    same_device(sol, *n_atoms);
+    TORCH_CHECK(n_atoms->dim() == 2 && n_atoms->size(0) == n_rows && n_atoms->size(1) == maxit,
+                "n_atoms must be [n_rows, maxit], got ", n_atoms->sizes());
+  }
+  const auto [ws, ws_bytes] = byte_workspace(sol, workspace);
+  chk(ainp_spain_omp(dev<double>(sol, "sol", at::kDouble), n_rows, w, tab[0], tab[1], (int)w,
+                     (int)red, (int)s, (int)r, epsilon, (int)maxit, errdb, tab[2], h, na, ws,
+                     ws_bytes, stream_of(sol)),
+      "spain_omp");
+}
+
 // SPAIN over whole signals with a Gabor frame and an optional unitary basis
 void spain_learned(const Tensor& x, const Tensor& observed, int64_t w, int64_t a, int64_t M,
                    const OptT& basis, int64_t algorithm, int64_t s, int64_t r, double epsilon,
@@ -2061,6 +2094,9 @@ TORCH_LIBRARY(ainp, m) {
   m.def("spain(Tensor(a!) sol, Tensor gap_start, Tensor gap_len, int red, int algorithm, int s, "
         "int r, float epsilon, int maxit, Tensor(b!) iters, Tensor(c!)? obj_history, "
         "Tensor? workspace) -> ()");
+  m.def("spain_omp(Tensor(a!) sol, Tensor gap_start, Tensor gap_len, int red, int s, int r, "
+        "float epsilon, int maxit, float errdb, Tensor(b!) iters, Tensor(c!)? obj_history, "
+        "Tensor(d!)? n_atoms, Tensor? workspace) -> ()");
   m.def("spain_learned(Tensor(a!) x, Tensor observed, int w, int a, int M, Tensor? basis, "
         "int algorithm, int s, int r, float epsilon, int maxit, Tensor(b!) iters, "
         "Tensor(c!)? obj_history, Tensor? workspace) -> ()");
@@ -2155,6 +2191,7 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("janssen_windows", &janssen_windows);
   m.impl("janssen_ola", &janssen_ola);
   m.impl("spain", &spain);
+  m.impl("spain_omp", &spain_omp);
   m.impl("spain_learned", &spain_learned);
 }
 
@@ -2250,5 +2287,6 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("janssen_windows", torch::CppFunction::makeFallthrough());
   m.impl("janssen_ola", torch::CppFunction::makeFallthrough());
   m.impl("spain", torch::CppFunction::makeFallthrough());
+  m.impl("spain_omp", torch::CppFunction::makeFallthrough());
   m.impl("spain_learned", torch::CppFunction::makeFallthrough());
 }

@@ -235,15 +235,18 @@ def run_spain_evaluation(input_dir, output_dir, algorithm="aspain", w=4096, a=10
     """The sparsity row of the same comparison (references/spain) on the clips
     and the gap of inpaint(): algorithm "aspain" or "sspain", Hann windows of w
     samples every a samples, **solver handed to spain_inpaint (red, s, r,
-    epsilon, maxit).  Every .flac of input_dir gets the 80 ms gap at 2.0 s, all
-    gaps are filled in one batch, and each result is written as
-    <stem>_<algorithm>_inpainted.flac.  Returns {filename: gap SDR in dB},
-    measured before save_audio's normalisation and 16-bit quantisation."""
+    epsilon, maxit, f_update, omp_errdb).  Every .flac of input_dir gets the
+    80 ms gap at 2.0 s, all gaps are filled in one batch, and each result is
+    written as <stem>_<algorithm>_inpainted.flac, <stem>_sspain_omp_inpainted.flac
+    with f_update "OMP".  Returns {filename: gap SDR in dB}, measured before
+    save_audio's normalisation and 16-bit quantisation."""
     from models.AudioReg import spain_inpaint
     if algorithm not in SPAIN_ALGORITHMS:
         raise ValueError(f"algorithm must be one of {SPAIN_ALGORITHMS}, got {algorithm!r}")
+    f_update = solver.get("f_update", "H")
+    omp = isinstance(f_update, str) and f_update.upper() == "OMP"
     return _evaluate_gap_filler(
-        input_dir, output_dir, algorithm,
+        input_dir, output_dir, algorithm + ("_omp" if omp else ""),
         lambda clean, masks: spain_inpaint(clean, masks, algorithm=algorithm, w=w, a=a, **solver))
 
 
