@@ -217,7 +217,9 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(
 
 // ------------------------------------------------------------ VGG19 input gradient
 // MaxPool2d(2, 2) backward with torch's CPU argmax rule (first maximum in
-// row-major window order; NaN wins): g [NC, H/2, W/2] -> gx [NC, H, W].
+// row-major window order; a NaN replaces whatever came before it, an earlier
+// NaN included, so the last NaN of a window takes the gradient):
+// g [NC, H/2, W/2] -> gx [NC, H, W].
 __global__ void maxpool2_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x,
                                     int H, int W, int64_t total, float* __restrict__ gx) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -237,7 +239,6 @@ __global__ void maxpool2_bwd_kernel(const float* __restrict__ g, const float* __
       if (c > mx || isnan(c)) {
         mx = c;
         best = k;
-        if (isnan(c)) break;
       }
     }
     if (best == ((yy & 1) << 1 | (xx & 1))) v = g[(nc * Ho + oy) * Wo + ox];

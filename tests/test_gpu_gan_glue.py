@@ -3,7 +3,11 @@ loss.hip through their ainp.ops wrappers), which the Discriminator / VGGLoss /
 GanTrainer goldens reach only at the fixture shapes: each op against a plain
 float64 torch evaluation (tests/gan_glue_ref.py for the spectral norm, pinned
 to torch.nn.utils.spectral_norm in test_cpu_gan_glue_ref.py; oracle/gan_ref.py
-for the VGG input), at the smallest shapes that reach every tail.
+for the VGG input), at the smallest shapes that reach every tail.  Of
+gan_bwd.hip this file holds vgg_prep_bwd, conv_weight_flip_t and
+affine_leaky_out; that file's remaining ops (BatchNorm + LeakyReLU backward,
+activation + crop backward, the PartialConv sources, maxpool2_bwd and the sign
+gradients) are in tests/test_gpu_gan_bwd_edges.py, under the same bounds.
 
 Bounds.  Copies, selections and maxima: torch.equal with the float32 torch
 result.  Reduced scalars: 1e-6 relative (as test_l1_pow10_loss,
