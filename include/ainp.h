@@ -419,6 +419,51 @@ int ainp_spain_learned(double* x, const uint8_t* observed, int64_t L, int64_t n_
 size_t ainp_spain_learned_workspace(int64_t L, int64_t n_signals, int w, int a, int M,
                                     int has_basis, int algorithm);
 
+/* The analysis of ainp_spain_learned alone (the dgt(x, g) of
+ * references/basisopt/a_spain_learned.m:43 and s_spain_learned.m, through the
+ * same kernels): coef [n_signals L / a][K] complex (re, im interleaved), frame n
+ * of signal s at row s L / a + n, = column n of dgt(x_s, g) with g the periodic
+ * Hann window.  x [n_signals][L] is read as it is (no mask).  Supported: the
+ * (L, w, a, M) range of ainp_spain_learned, else AINP_EINVAL naming the rule
+ * without a launch.  workspace: 16-byte aligned, at least
+ * ainp_spain_dgt_workspace(n_signals, w) bytes (0 for a bad shape). */
+int ainp_spain_dgt(const double* x, int64_t L, int64_t n_signals, int w, int a, int M,
+                   double* coef, void* workspace, size_t ws_bytes, void* stream);
+size_t ainp_spain_dgt_workspace(int64_t n_signals, int w);
+
+/* Learning the unitary basis of ainp_spain_learned from training spectra
+ * (references/basisopt/basis_opt_new.m, whole file, without CVX / SDPT3;
+ * csrc/basis_learn.hip).  Float64.  X [K][M_tr] complex (re, im
+ * interleaved), the training index contiguous.  With Aopt = I, Y = X, level =
+ * level_init and the loop of basis_opt_new.m:43-74: every solve minimises
+ * sum |Y + j 2 pi A Y| over Hermitian tridiagonal A with every |entry| <= level
+ * (basis_opt_new.m:48-54) by a diagonally preconditioned primal-dual iteration
+ * from zero, stopped at the first multiple of `check` (or at max_iters) where
+ * P - D <= gap_tol P for the primal value P and the dual value D; then Aopt <-
+ * expm(j 2 pi A) Aopt and Y <- expm(j 2 pi A) Y as a Taylor action (the smallest
+ * n with (6 pi level)^n / n! < 1e-18 terms), sparsity = sum |Y|.  An update is
+ * kept while sparsity < sparsity_old (strict); otherwise it is undone and the
+ * level halved; the loop ends when level <= epsilon or after cnt_max solves
+ * (the last of which is kept untested, as in the reference).
+ * Outputs: U [K][K] complex row-major (re, im interleaved); sparsity [2] =
+ * (|X|_1, |U X|_1 recomputed from U); trace [cnt_max][6] = (level, iterations,
+ * P, D, sparsity after the update, 1 kept / 0 undone) per solve, NaN past the
+ * last.  Launches are the barriers (no cooperative launch, no float atomics),
+ * every sum is added in a fixed order: the same bits on every call.  The host
+ * reads the solver's stop flag every 32 checks only to stop issuing launches
+ * (AINP_BASIS_LEARN_CHUNK sets another interval, 0: never; no result changes)
+ * and one scalar after each solve for the accept / reject decision.
+ * Supported: K = M / 2 + 1 with M a power of two, 8 <= M <= 2048; M_tr >= 1;
+ * K M_tr <= 2^26; epsilon > 0; 0 < level_init <= 0.25; 1 <= cnt_max <= 64;
+ * gap_tol >= 0; 1 <= check <= max_iters <= 2^20.  Anything else is AINP_EINVAL
+ * naming the rule, without a launch.  workspace: 16-byte aligned, at least
+ * ainp_basis_learn_workspace(K, M_tr) bytes (0 for a bad shape). */
+int ainp_basis_learn(const double* X, int K, int64_t M_tr, double level_init, double epsilon,
+                     int cnt_max, double gap_tol, int max_iters, int check, double* U,
+                     double* sparsity, double* trace, void* workspace, size_t ws_bytes,
+                     void* stream);
+size_t ainp_basis_learn_workspace(int K, int64_t M_tr);
+
 /* ------------------------------------------------------------------------ */
 /* fp32 GEMM on MFMA (fp32-accurate bf16 split by default, exact f32 on flag) */
 /* ------------------------------------------------------------------------ */

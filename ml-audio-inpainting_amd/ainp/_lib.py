@@ -278,6 +278,12 @@ _SIGS = {
                                    c_int, c_double, c_int, P, P, P, c_size_t, P]),
     "ainp_spain_learned_workspace": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int, c_int,
                                                 c_int]),
+    "ainp_spain_dgt": (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "ainp_spain_dgt_workspace": (c_size_t, [c_int64, c_int]),
+    # learning the unitary basis of spain_learned (csrc/basis_learn.hip)
+    "ainp_basis_learn": (c_int, [P, c_int, c_int64, c_double, c_double, c_int, c_double, c_int,
+                                 c_int, P, P, P, P, c_size_t, P]),
+    "ainp_basis_learn_workspace": (c_size_t, [c_int, c_int64]),
 }
 
 EXPORTED = tuple(_SIGS)

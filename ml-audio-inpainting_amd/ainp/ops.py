@@ -2392,3 +2392,49 @@ def spain_learned(x, observed, basis=None, algorithm="aspain", w=1024, a=256, M=
         _T.spain_learned(x, observed, w, a, M, basis, alg, int(s), int(r), float(epsilon), maxit,
                          iters, hist, ws)
     return iters, hist
+
+
+def spain_dgt(x, w=1024, a=256, M=None):
+    """ainp_spain_dgt: the analysis of spain_learned alone.  x [n_signals, L]
+    float64 cuda, L a multiple of M (None: 2 w).  Returns the coefficients
+    [n_signals, L / a, K, 2] float64 (re, im): frame n of a signal is column n
+    of dgt(x, g) with the periodic Hann window g."""
+    from . import spain_learned as _sl
+    _req(x, "x", dtype=torch.float64)
+    w, a, M, _ = _sl.check_args(w, a, M)
+    if x.dim() != 2:
+        raise ValueError("x must be [n_signals, L]")
+    nsig, L = x.shape
+    if L < M or L % M or L > _sl.L_MAX:
+        raise ValueError(f"L must be a multiple of M = {M} in [M, {_sl.L_MAX}], got L = {L}")
+    N, K = L // a, M // 2 + 1
+    coef = torch.empty((nsig * N, K, 2), device=x.device, dtype=torch.float64)
+    if nsig:
+        ws = torch.empty(_lib.lib.ainp_spain_dgt_workspace(nsig, w), device=x.device,
+                         dtype=torch.uint8)
+        _T.spain_dgt(x, w, a, M, coef, ws)
+    return coef.reshape(nsig, N, K, 2)
+
+
+def basis_learn(X, level_init=0.02, epsilon=None, cnt_max=20, gap_tol=1e-5, max_iters=20000,
+                check=100):
+    """ainp_basis_learn: the unitary basis that sparsifies the training spectra
+    X [K, M_tr, 2] float64 cuda (re, im), K = M / 2 + 1 (basis_opt_new.m without
+    CVX).  epsilon None: level_init / 16.  Returns (U [K, K, 2], sparsity [2] =
+    (before, after), trace [cnt_max, 6] = (level, iterations, P, D, sparsity after
+    the update, kept) per solve, NaN past the last), all float64 cuda."""
+    from . import basis_learn as _bl
+    _req(X, "X", dtype=torch.float64)
+    if X.dim() != 3 or X.shape[2] != 2:
+        raise ValueError(f"X must be [K, M_tr, 2] (re, im), got {tuple(X.shape)}")
+    K, Mt = int(X.shape[0]), int(X.shape[1])
+    level_init, epsilon, cnt_max, gap_tol, max_iters, check = _bl.check_args(
+        K, Mt, level_init, epsilon, cnt_max, gap_tol, max_iters, check)
+    dv = X.device
+    U = torch.empty((K, K, 2), device=dv, dtype=torch.float64)
+    sparsity = torch.empty(2, device=dv, dtype=torch.float64)
+    trace = torch.empty((cnt_max, 6), device=dv, dtype=torch.float64)
+    ws = torch.empty(_lib.lib.ainp_basis_learn_workspace(K, Mt), device=dv, dtype=torch.uint8)
+    _T.basis_learn(X, level_init, epsilon, cnt_max, gap_tol, max_iters, check, U, sparsity, trace,
+                   ws)
+    return U, sparsity, trace

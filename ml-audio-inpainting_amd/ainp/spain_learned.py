@@ -6,8 +6,9 @@ One ADMM loop runs over the whole signal with a Gabor frame (periodic Hann
 window of w samples every a samples, M channels) and one stopping rule; the
 coefficients of every frame are rotated by a unitary basis before the hard
 threshold.  Without a basis this is the global, non-segmented SPAIN row.  The
-basis is an input: basis_opt_new.m, which learns it, is not ported.  (The
-reference's OMP coefficient update exists only in the segment-wise sspain.m:
+basis is an input, or basis="learn": basis_opt_new.m on the signal's own
+reliable frames (ainp.basis_learn).  (The reference's OMP
+coefficient update exists only in the segment-wise sspain.m:
 ainp.spain.spain_inpaint(f_update="OMP"))
 
 Signals are padded with observed zeros to a multiple of M and grouped by padded
@@ -100,7 +101,11 @@ def spain_learned_inpaint(signal, mask=None, basis=None, algorithm="aspain", w=1
     Gabor frame of the periodic Hann window of w samples, hop a, M channels (None:
     2 w); basis: a unitary complex [K, K] array or tensor, K = M / 2 + 1, applied
     to every frame's coefficients before the threshold (None: the identity, the
-    global SPAIN row).
+    global SPAIN row).  basis="learn": one basis per signal, learned from the
+    signal's own reliable frames by ainp.basis_learn.spain_learn_basis with its
+    defaults; a dict instead of "learn" holds keyword arguments for it (context,
+    level_init, epsilon, cnt_max, gap_tol, max_iters, check).  Each such signal
+    is its own launch sequence.
 
     Input layouts, mask / NaN conventions and the return layout are
     spain_inpaint's; only missing samples are written, and there is no limit on
@@ -115,18 +120,28 @@ def spain_learned_inpaint(signal, mask=None, basis=None, algorithm="aspain", w=1
     from . import ops
     algorithm_id(algorithm)
     w, a, M, maxit = check_args(w, a, M, s, r, epsilon, maxit)
-    U = None if basis is None else check_basis(basis, M)
+    learn = {} if isinstance(basis, str) and basis == "learn" else basis
+    learn = dict(learn) if isinstance(learn, dict) else None
+    if isinstance(basis, str) and learn is None:
+        raise ValueError(f'basis must be None, a unitary matrix, "learn" or a dict, got {basis!r}')
+    U = None if basis is None or learn is not None else check_basis(basis, M)
     sigs, masks, kind = _normalise(signal, mask)
     res = [x.copy() for x in sigs]
     iters = [0] * len(sigs)
     objs = [np.full(maxit, np.nan) for _ in sigs]
     todo = [i for i, m in enumerate(masks) if not m.all()]
-    groups = plan_groups([len(sigs[i]) for i in todo], M)
-    Ud = None
-    if U is not None and groups:
-        Ud = torch.from_numpy(U.view(np.float64).reshape(U.shape + (2,))).to(device)
-    for L, members in groups.items():
-        idx = [todo[j] for j in members]
+    to_device = lambda V: torch.from_numpy(V.view(np.float64).reshape(V.shape + (2,))).to(device)
+    if learn is None:
+        groups = plan_groups([len(sigs[i]) for i in todo], M)
+        Ud = to_device(U) if U is not None and groups else None
+        runs = [(L, [todo[j] for j in members], Ud) for L, members in groups.items()]
+    else:
+        from .basis_learn import spain_learn_basis
+        runs = []
+        for i in todo:
+            Ui = check_basis(spain_learn_basis(sigs[i], masks[i], w, a, M, device=device, **learn), M)
+            runs.append((padded_length(len(sigs[i]), M), [i], to_device(Ui)))
+    for L, idx, Ud in runs:
         x = np.zeros((len(idx), L))
         obs = np.ones((len(idx), L), np.uint8)
         for row, i in enumerate(idx):

@@ -39,6 +39,7 @@
 // quarter wave 514 x 8 = 4112: 21 KiB.  sl_gemm: 2 x 16 x 33 x 16 = 16.5 KiB.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
@@ -602,4 +603,46 @@ extern "C" int ainp_spain_learned(double* x, const uint8_t* observed, int64_t L,
     }
   }
   return check_launch("ainp_spain_learned");
+}
+
+// The analysis alone: dgt(x, g) of every signal through sl_windows and
+// sl_forward, for callers that need the coefficients themselves (the training
+// columns of ainp_basis_learn).  workspace: g, gd and the (clear) stop flags.
+static size_t dgt_ws_bytes(int64_t n_signals, int w) {
+  return (((size_t)2 * w * sizeof(double) + 15) & ~(size_t)15) + sizeof(int) * (size_t)n_signals;
+}
+
+extern "C" size_t ainp_spain_dgt_workspace(int64_t n_signals, int w) {
+  if (n_signals < 1 || w < SL_WMIN || w > SL_MMAX) return 0;
+  return dgt_ws_bytes(n_signals, w);
+}
+
+extern "C" int ainp_spain_dgt(const double* x, int64_t L, int64_t n_signals, int w, int a, int M,
+                              double* coef, void* workspace, size_t ws_bytes, void* stream) {
+  if (!x || !coef || n_signals < 0) return record_msg("ainp_spain_dgt: bad argument");
+  if (const char* rule = sl_shape_rule(L, w, a, M)) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "ainp_spain_dgt%s", rule + sizeof("ainp_spain_learned") - 1);
+    return record_msg(msg);
+  }
+  const int64_t N = L / a, NF = n_signals * N;
+  if (NF > 0x7fffffff) return record_msg("ainp_spain_dgt: too many signals (n_signals L / a < 2^31)");
+  if (n_signals == 0) return AINP_OK;
+  if (!workspace || ws_bytes < dgt_ws_bytes(n_signals, w) || ((uintptr_t)workspace & 15))
+    return record_msg("ainp_spain_dgt: workspace too small or not 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  double* g = static_cast<double*>(workspace);
+  double* gd = g + w;
+  int* done = reinterpret_cast<int*>(static_cast<unsigned char*>(workspace) +
+                                     dgt_ws_bytes(n_signals, w) - sizeof(int) * (size_t)n_signals);
+  hipError_t e = hipMemsetAsync(done, 0, sizeof(int) * (size_t)n_signals, st);
+  if (e != hipSuccess) return record_error(e, "ainp_spain_dgt");
+  int lgN = 0;
+  while ((2 << lgN) < M) ++lgN;   // M / 2 = 1 << lgN
+  const int nF = M / 2 + M / 64 + 2, nCos = (M / 4 + 2) & ~1;
+  const size_t lds = ((size_t)2 * nF + nCos) * sizeof(double);
+  hipLaunchKernelGGL(sl_windows, dim3(1), dim3(SL_NT), 0, st, g, gd, w, a, M);
+  hipLaunchKernelGGL(sl_forward, dim3((unsigned)NF), dim3(SL_NT), lds, st, x, (const double*)nullptr,
+                     g, reinterpret_cast<cplx*>(coef), L, (int)N, w, a, M, lgN, nF, done);
+  return check_launch("ainp_spain_dgt");
 }

@@ -456,6 +456,51 @@ void spain_learned(const Tensor& x, const Tensor& observed, int64_t w, int64_t a
       "spain_learned");
 }
 
+// dgt(x, g) of whole signals: the analysis of spain_learned alone
+void spain_dgt(const Tensor& x, int64_t w, int64_t a, int64_t M, const Tensor& coef,
+               const OptT& workspace) {
+  GUARD(x);
+  TORCH_CHECK(x.dim() == 2, "x must be [n_signals, L]");
+  TORCH_CHECK(w >= 1 && w <= INT32_MAX && a >= 1 && a <= INT32_MAX && M >= 2 && M <= INT32_MAX,
+              "w, a and M must be positive");
+  const int64_t n_sig = x.size(0), L = x.size(1);
+  same_device(x, coef);
+  TORCH_CHECK(coef.dim() == 3 && coef.size(0) == n_sig * (L / a) && coef.size(1) == M / 2 + 1 &&
+                  coef.size(2) == 2,
+              "coef must be [n_signals L / a, M / 2 + 1, 2] (re, im), got ", coef.sizes());
+  const auto [ws, ws_bytes] = byte_workspace(x, workspace);
+  chk(ainp_spain_dgt(dev<double>(x, "x", at::kDouble), L, n_sig, (int)w, (int)a, (int)M,
+                     dev<double>(coef, "coef", at::kDouble), ws, ws_bytes, stream_of(x)),
+      "spain_dgt");
+}
+
+// the unitary basis of spain_learned from training spectra
+void basis_learn(const Tensor& X, double level_init, double epsilon, int64_t cnt_max,
+                 double gap_tol, int64_t max_iters, int64_t check, const Tensor& U,
+                 const Tensor& sparsity, const Tensor& trace, const OptT& workspace) {
+  GUARD(X);
+  TORCH_CHECK(X.dim() == 3 && X.size(2) == 2, "X must be [K, M_tr, 2] (re, im), got ", X.sizes());
+  const int64_t K = X.size(0), Mt = X.size(1);
+  TORCH_CHECK(K <= INT32_MAX && cnt_max >= 1 && cnt_max <= INT32_MAX && max_iters >= 1 &&
+                  max_iters <= INT32_MAX && check >= 1 && check <= INT32_MAX,
+              "cnt_max, max_iters and check must be positive");
+  same_device(X, U);
+  same_device(X, sparsity);
+  same_device(X, trace);
+  TORCH_CHECK(U.dim() == 3 && U.size(0) == K && U.size(1) == K && U.size(2) == 2,
+              "U must be [K, K, 2] (re, im), got ", U.sizes());
+  numel_is(sparsity, 2, "sparsity");
+  TORCH_CHECK(trace.dim() == 2 && trace.size(0) == cnt_max && trace.size(1) == 6,
+              "trace must be [cnt_max, 6], got ", trace.sizes());
+  const auto [ws, ws_bytes] = byte_workspace(X, workspace);
+  chk(ainp_basis_learn(dev<double>(X, "X", at::kDouble), (int)K, Mt, level_init, epsilon,
+                       (int)cnt_max, gap_tol, (int)max_iters, (int)check,
+                       dev<double>(U, "U", at::kDouble),
+                       dev<double>(sparsity, "sparsity", at::kDouble),
+                       dev<double>(trace, "trace", at::kDouble), ws, ws_bytes, stream_of(X)),
+      "basis_learn");
+}
+
 // ------------------------------------------------------------------- GEMM
 void gemm(int64_t M, int64_t N, int64_t K, double alpha, at::TensorList A, int64_t sam,
           int64_t sak, int64_t strideA, at::TensorList B, int64_t sbk, int64_t sbn,
@@ -2100,6 +2145,10 @@ TORCH_LIBRARY(ainp, m) {
   m.def("spain_learned(Tensor(a!) x, Tensor observed, int w, int a, int M, Tensor? basis, "
         "int algorithm, int s, int r, float epsilon, int maxit, Tensor(b!) iters, "
         "Tensor(c!)? obj_history, Tensor? workspace) -> ()");
+  m.def("spain_dgt(Tensor x, int w, int a, int M, Tensor(a!) coef, Tensor? workspace) -> ()");
+  m.def("basis_learn(Tensor X, float level_init, float epsilon, int cnt_max, float gap_tol, "
+        "int max_iters, int check, Tensor(a!) U, Tensor(b!) sparsity, Tensor(c!) trace, "
+        "Tensor? workspace) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
@@ -2193,6 +2242,8 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("spain", &spain);
   m.impl("spain_omp", &spain_omp);
   m.impl("spain_learned", &spain_learned);
+  m.impl("spain_dgt", &spain_dgt);
+  m.impl("basis_learn", &basis_learn);
 }
 
 // The ops write through raw device pointers like the C ABI; autograd is the
@@ -2289,4 +2340,6 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("spain", torch::CppFunction::makeFallthrough());
   m.impl("spain_omp", torch::CppFunction::makeFallthrough());
   m.impl("spain_learned", torch::CppFunction::makeFallthrough());
+  m.impl("spain_dgt", torch::CppFunction::makeFallthrough());
+  m.impl("basis_learn", torch::CppFunction::makeFallthrough());
 }

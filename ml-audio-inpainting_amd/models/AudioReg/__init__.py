@@ -8,11 +8,13 @@ csrc/janssen_windows.hip, csrc/ar_extrapolate.hip); the sparsity-based A-SPAIN
 and S-SPAIN of references/spain (ainp/spain.py -> csrc/spain.hip between the
 same gather and overlap-add) and their whole-signal form with a learned
 unitary basis of references/basisopt (ainp/spain_learned.py ->
-csrc/spain_learned.hip); and the gap SDR of train.m:196 /
+csrc/spain_learned.hip), the basis itself learned as basis_opt_new.m learns it
+(ainp/basis_learn.py -> csrc/basis_learn.hip); and the gap SDR of train.m:196 /
 model_eval.m:60."""
 from ainp.janssen import ar_extrapolate, gap_sdr, janssen_inpaint, janssen_windowed
+from ainp.basis_learn import learn_basis, spain_learn_basis, spain_training_frames
 from ainp.spain import spain_inpaint
 from ainp.spain_learned import spain_learned_inpaint
 
 __all__ = ["janssen_inpaint", "janssen_windowed", "ar_extrapolate", "spain_inpaint", "gap_sdr",
-           "spain_learned_inpaint"]
+           "spain_learned_inpaint", "learn_basis", "spain_learn_basis", "spain_training_frames"]

@@ -255,8 +255,10 @@ def run_spain_learned_evaluation(input_dir, output_dir, basis=None, algorithm="a
     """SPAIN over the whole signal (references/basisopt: a_spain_learned.m /
     s_spain_learned.m) on the clips and the gap of inpaint(): algorithm "aspain"
     or "sspain", the Gabor frame of a Hann window of w samples every a samples,
-    basis None (the global SPAIN row) or a unitary [K, K] matrix (the learned
-    row), **solver handed to spain_learned_inpaint (M, s, r, epsilon, maxit).
+    basis None (the global SPAIN row), a unitary [K, K] matrix or "learn" / a
+    dict of learning options (the learned row; "learn": one basis per clip from
+    its own reliable frames, as spain_learned_inpaint learns it), **solver handed
+    to spain_learned_inpaint (M, s, r, epsilon, maxit).
     Each result is written as <stem>_<algorithm>_global_inpainted.flac without a
     basis and <stem>_<algorithm>_learned_inpainted.flac with one.  Returns
     {filename: gap SDR in dB}, measured as run_spain_evaluation measures it."""
