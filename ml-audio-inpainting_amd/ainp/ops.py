@@ -2297,6 +2297,27 @@ def janssen_ola(sol, row_history, row_tab, gap_start, gap_len, gap_off, gap_tab,
 
 
 # ================================================================== SPAIN
+def _spain_rows(sol, gap_start, gap_len):
+    """The checks of sol [n_rows, w] and the rows' runs that the two window
+    solvers share -> (n_rows, w, gap_start, gap_len as int64 numpy)."""
+    _req(sol, "sol", dtype=torch.float64)
+    if sol.dim() != 2:
+        raise ValueError("sol must be [n_rows, w]")
+    nrows, w = sol.shape
+    gs = np.asarray(gap_start, dtype=np.int64).reshape(-1)
+    gl = np.asarray(gap_len, dtype=np.int64).reshape(-1)
+    if gs.size != nrows or gl.size != nrows:
+        raise ValueError("gap_start and gap_len need one entry per row")
+    _check_runs(gs, gl, w, "run must lie inside its window")
+    return nrows, int(w), gs, gl
+
+
+def _check_signal_length(L, M, L_max):
+    """L of the whole-signal solvers: a multiple of M in [M, L_max]."""
+    if L < M or L % M or L > L_max:
+        raise ValueError(f"L must be a multiple of M = {M} in [M, {L_max}], got L = {L}")
+
+
 def spain(sol, gap_start, gap_len, algorithm="aspain", red=2, s=1, r=1, epsilon=0.1, maxit=None,
           return_history=False):
     """ainp_spain: A-SPAIN or S-SPAIN on a batch of windows, float64, one
@@ -2307,20 +2328,12 @@ def spain(sol, gap_start, gap_len, algorithm="aspain", red=2, s=1, r=1, epsilon=
     maxit None: ceil(floor(w red / 2 + 1) r / s).  Returns (iters int32
     [n_rows], objective [n_rows, maxit] float64 or None; NaN after a row's
     last pass)."""
-    _req(sol, "sol", dtype=torch.float64)
-    if sol.dim() != 2:
-        raise ValueError("sol must be [n_rows, w]")
-    nrows, w = sol.shape
+    nrows, w, gs, gl = _spain_rows(sol, gap_start, gap_len)
     alg = _sp.algorithm_id(algorithm)
     maxit = _sp.check_args(w, red, s, r, epsilon, maxit)
-    gs = np.asarray(gap_start, dtype=np.int64).reshape(-1)
-    gl = np.asarray(gap_len, dtype=np.int64).reshape(-1)
-    if gs.size != nrows or gl.size != nrows:
-        raise ValueError("gap_start and gap_len need one entry per row")
-    _check_runs(gs, gl, w, "run must lie inside its window")
     dv = sol.device
     iters, hist, ws = _row_outputs(dv, nrows, (nrows, maxit) if return_history else None,
-                                   _lib.lib.ainp_spain_workspace(nrows, int(w), int(red), alg))
+                                   _lib.lib.ainp_spain_workspace(nrows, w, int(red), alg))
     if nrows:
         _T.spain(sol, _dev_i32(gs, dv), _dev_i32(gl, dv), int(red), alg, int(s), int(r),
                  float(epsilon), maxit, iters, hist, ws)
@@ -2336,19 +2349,11 @@ def spain_omp(sol, gap_start, gap_len, red=2, s=1, r=1, epsilon=0.1, maxit=None,
     cap on the least squares' real unknowns holds.  Returns (iters int32
     [n_rows], objective [n_rows, maxit] float64 or None, atoms [n_rows, maxit]
     int32 or None: the atoms chosen in every pass, -1 after a row's last)."""
-    _req(sol, "sol", dtype=torch.float64)
-    if sol.dim() != 2:
-        raise ValueError("sol must be [n_rows, w]")
-    nrows, w = sol.shape
+    nrows, w, gs, gl = _spain_rows(sol, gap_start, gap_len)
     maxit = _sp.check_omp_args(w, red, s, r, epsilon, maxit, errdb)
-    gs = np.asarray(gap_start, dtype=np.int64).reshape(-1)
-    gl = np.asarray(gap_len, dtype=np.int64).reshape(-1)
-    if gs.size != nrows or gl.size != nrows:
-        raise ValueError("gap_start and gap_len need one entry per row")
-    _check_runs(gs, gl, w, "run must lie inside its window")
     dv = sol.device
     iters, hist, ws = _row_outputs(dv, nrows, (nrows, maxit) if return_history else None,
-                                   _lib.lib.ainp_spain_omp_workspace(nrows, int(w), int(red)))
+                                   _lib.lib.ainp_spain_omp_workspace(nrows, w, int(red)))
     atoms = (torch.full((nrows, maxit), -1, device=dv, dtype=torch.int32)
              if return_history else None)
     if nrows:
@@ -2375,8 +2380,7 @@ def spain_learned(x, observed, basis=None, algorithm="aspain", w=1024, a=256, M=
     if x.dim() != 2 or observed.shape != x.shape:
         raise ValueError("x and observed must both be [n_signals, L]")
     nsig, L = x.shape
-    if L < M or L % M or L > _sl.L_MAX:
-        raise ValueError(f"L must be a multiple of M = {M} in [M, {_sl.L_MAX}], got L = {L}")
+    _check_signal_length(L, M, _sl.L_MAX)
     K = M // 2 + 1
     if basis is not None:
         _req(basis, "basis", dtype=torch.float64)
@@ -2405,8 +2409,7 @@ def spain_dgt(x, w=1024, a=256, M=None):
     if x.dim() != 2:
         raise ValueError("x must be [n_signals, L]")
     nsig, L = x.shape
-    if L < M or L % M or L > _sl.L_MAX:
-        raise ValueError(f"L must be a multiple of M = {M} in [M, {_sl.L_MAX}], got L = {L}")
+    _check_signal_length(L, M, _sl.L_MAX)
     N, K = L // a, M // 2 + 1
     coef = torch.empty((nsig * N, K, 2), device=x.device, dtype=torch.float64)
     if nsig:

@@ -18,6 +18,11 @@ int record_msg(const char* msg) {
   snprintf(g_last_error, sizeof(g_last_error), "%s", msg);
   return AINP_EINVAL;
 }
+int record_bad_argument(const char* fn, const char* rule) {
+  if (rule) snprintf(g_last_error, sizeof(g_last_error), "%s: bad argument (%s)", fn, rule);
+  else snprintf(g_last_error, sizeof(g_last_error), "%s: bad argument", fn);
+  return AINP_EINVAL;
+}
 }  // namespace ainp
 
 extern "C" int ainp_abi_version(void) { return 1; }

@@ -10,6 +10,8 @@ namespace ainp {
 // Record the failing hip error for ainp_last_error(); returns AINP_ELAUNCH.
 int record_error(hipError_t e, const char* where);
 int record_msg(const char* msg);
+// "<fn>: bad argument (<rule>)", or without a rule "<fn>: bad argument"
+int record_bad_argument(const char* fn, const char* rule = nullptr);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

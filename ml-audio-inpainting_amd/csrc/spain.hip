@@ -12,8 +12,10 @@
 // row's gap in `sol`, which is the result.
 //
 // One workgroup owns one row for all passes; rows stop at different passes and
-// share nothing.  What lives where (the transforms, the slots, the sum and the
-// select are in spain_fft.h, which spain_learned.hip uses too):
+// share nothing.  What lives where (spain_fft.h: the transforms, the slots, the
+// quarter wave, the sum and the select with its tie rule; spain_window.h: the
+// steps of the window loop that spain_omp.hip shares; spain_plan.h: the limits,
+// the LDS plan and the lane route, on the host):
 //   * the length-M real transforms are N = M/2 point complex transforms on
 //     split re / im arrays in LDS, in place: forward decimation-in-frequency
 //     from natural to bit-reversed order, inverse decimation-in-time back, two
@@ -49,40 +51,17 @@
 //                                             samples never change; the run is
 //                                             known by its bounds, no flags)
 //   cos      (2048 + 1) x 8       = 16392     the quarter wave
-//   static   histogram 1024 + wave sums and the select's result < 256
+//   static   histogram 1024 + wave sums and the select's result < 256; 40 of padding
 // 117 KiB of the 160 KiB: one workgroup per CU there.  N <= 1024 runs 256 lanes
 // with 2 slots a lane, longer transforms 512 lanes with up to 4: at 1024 lanes
 // and 2 slots the 128 registers a lane has left spill (196 bytes of scratch a
 // lane in A-SPAIN), and A-SPAIN measured 6 % (one row) to 16 % (256 rows) slower
 // than at 512 lanes, S-SPAIN 5 % faster.
-#include <algorithm>
 #include <cmath>
 
-#include "ar_limits.h"
-#include "common.h"
-#include "spain_fft.h"
+#include "spain_window.h"
 
 namespace ainp {
-
-constexpr int SP_WMIN = 8, SP_WMAX = 4096, SP_MMAX = 8192;
-// Per lane: EPL spectrum slots, 2 EPL time-domain sample pairs, and NK = 2 EPL
-// + 1 half-spectrum bins to rank (template parameters of what follows).
-constexpr int SP_NMAX_256 = 1024;   // the longest transform the 256-lane kernel takes (EPL 2)
-constexpr int SP_NT_BIG = 512;      // lanes of the kernel for the longer ones, up to N = 4096
-constexpr int SP_EPL_BIG = 2048 / SP_NT_BIG;
-
-struct SpLds {
-  int nF, nRow, nCos;   // doubles: one of re / im, the row, the quarter wave
-  size_t bytes() const { return ((size_t)2 * nF + nRow + nCos) * sizeof(double); }
-};
-static SpLds sp_lds(int w, int M) {
-  SpLds l;
-  const int N = M / 2;
-  l.nF = N + N / 32 + 2;
-  l.nRow = w;
-  l.nCos = (M / 4 + 2) & ~1;
-  return l;
-}
 
 // H_k on a lane's slots: keep[e][0 / 1] for a / b, keepx for the Nyquist half
 // of slot 0.  V is the half spectrum to rank, bins 0 .. N.
@@ -112,32 +91,10 @@ __device__ void sp_hard_threshold(const SpSpec<EPL>& V, int N, int k, uint32_t* 
   member[SP_NK - 1] = tid == 0;   // the Nyquist bin, not halved
   key[SP_NK - 1] = tid == 0 ? (uint64_t)__double_as_longlong(V.a[0].im * V.a[0].im) : 0;
   bin[SP_NK - 1] = N;
-  if (k >= N + 1) {
-#pragma unroll
-    for (int i = 0; i < SP_NK; ++i) keep[i] = member[i];
-    __syncthreads();
-    return;
-  }
-  uint64_t prefix, prefix2 = 0;
-  int shift, need, have, shift2 = 0;
-  sp_select<NT, SP_NK>(key, member, k, 56, hist, sel, tid, prefix, shift, need, have);
-  const bool tie = need < have;   // equal squared magnitudes, kept in part: lower bins first
-  bool member2[SP_NK];
-  uint64_t key2[SP_NK];
-#pragma unroll
-  for (int i = 0; i < SP_NK; ++i) {
-    member2[i] = member[i] && (key[i] >> shift) == (prefix >> shift);
-    key2[i] = (uint64_t)(0xffff - bin[i]);
-  }
-  if (tie) {
-    int need2, have2;
-    sp_select<NT, SP_NK>(key2, member2, need, 8, hist, sel, tid, prefix2, shift2, need2, have2);
-  }
-#pragma unroll
-  for (int i = 0; i < SP_NK; ++i) {
-    const bool above = member[i] && (key[i] >> shift) > (prefix >> shift);
-    keep[i] = above || (member2[i] && (!tie || (key2[i] >> shift2) >= (prefix2 >> shift2)));
-  }
+  const int count = N + 1;   // the half spectrum's bins, all members
+  sp_keep_largest<NT, SP_NK>(key, member, bin, k, count, hist, sel, tid, keep);
+  // sp_keep_largest's k >= count path has no barrier; S-SPAIN's caller needs one
+  if (k >= count) __syncthreads();
 }
 
 template <int EPL>
@@ -156,6 +113,25 @@ __device__ __forceinline__ void sp_apply(SpSpec<EPL>& V, const bool (&keep)[2 * 
   }
 }
 
+template <int NT>
+__device__ __forceinline__ bool sp_open(SpRow& R, double* ct, double* sol, int64_t stride,
+                                        const int32_t* gap_start, const int32_t* gap_len, int w,
+                                        int M, int maxit, int32_t* iters, double* obj_history,
+                                        int tid) {
+  const int64_t row = blockIdx.x;
+  R.gs = gap_start[row];
+  R.gl = gap_len[row];
+  R.hrow = obj_history ? obj_history + row * maxit : nullptr;
+  R.arow = nullptr;
+  if (!sp_run_ok(R.gs, R.gl, w)) {
+    sp_row_close<NT>(iters, R.hrow, R.arow, 0, maxit, tid);
+    return false;
+  }
+  R.x = sol + row * stride;
+  sp_row_load<NT>(R, ct, w, M, tid);
+  return true;
+}
+
 // grid: one workgroup of NT lanes per row.  dynamic LDS: SpLds.
 template <int NT, int ALG, int EPL>
 __global__ __launch_bounds__(NT) void spain_kernel(
@@ -168,26 +144,19 @@ __global__ __launch_bounds__(NT) void spain_kernel(
   __shared__ uint32_t hist[256];
   __shared__ double part[NT / 64];
   __shared__ int sel[4];
+  const int tid = threadIdx.x;
+  const int N = M / 2;
+  const int64_t row = blockIdx.x;
   double* re = reinterpret_cast<double*>(smem);
   double* im = re + nF;
   double* xr = im + nF;
   double* ct = xr + nRow;
-  const int tid = threadIdx.x;
-  const int64_t row = blockIdx.x;
-  const int N = M / 2;
-  const int gs = gap_start[row], gl = gap_len[row];
-  double* hrow = obj_history ? obj_history + row * maxit : nullptr;
-  // a row whose run does not lie in the window is left alone
-  if (gs < 0 || gl < 1 || gl > JN_HMAX || (int64_t)gs + gl > w) {
-    if (tid == 0) iters[row] = 0;
-    if (hrow)
-      for (int i = tid; i < maxit; i += NT) hrow[i] = NAN;
+  SpRow R;
+  R.xr = xr;
+  if (!sp_open<NT>(R, ct, sol, stride, gap_start, gap_len, w, M, maxit, iters, obj_history, tid))
     return;
-  }
-  double* x = sol + row * stride;
-  for (int j = tid; j <= M / 4; j += NT) ct[j] = cospi((double)(2 * j) / (double)M);
-  for (int i = tid; i < w; i += NT) xr[i] = (i >= gs && i - gs < gl) ? 0.0 : x[i];
-  __syncthreads();
+  const int gs = R.gs, gl = R.gl;
+  double* hrow = R.hrow;
 
   const SpFft f = {re, im, ct, N, lgN, M};
   const double fwd = 1.0 / sqrt((double)M);   // analysis: FFT_M / sqrt(M)
@@ -258,23 +227,11 @@ __global__ __launch_bounds__(NT) void spain_kernel(
       sp_merge<NT, EPL>(f, tid, ZB);
       __syncthreads();
       sp_dit<NT>(f, tid);
-#pragma unroll
-      for (int e = 0; e < SP_TPL; ++e) {
-        const int n = tid + e * NT;
-        if (n >= N || 2 * n >= w) continue;
-        const cplx c = f.ld(n);
-        const double d0 = c.re * inv - xr[2 * n], d1 = c.im * inv - xr[2 * n + 1];
-        acc += d0 * d0 + d1 * d1;
-      }
+      acc = sp_residual2<NT, SP_TPL>(f, R, w, inv, tid);
     }
     const double obj = sqrt(sp_sum<NT>(acc, part, tid));
     done = cnt;
-    if (hrow && tid == 0) hrow[cnt - 1] = obj;
-    if (obj <= best) {   // record the iterate the objective was evaluated on
-      best = obj;
-      for (int i = tid; i < gl; i += NT) x[gs + i] = xr[gs + i];
-    }
-    if (obj <= epsilon) break;
+    if (sp_record<NT>(R, obj, cnt, 0, best, epsilon, tid)) break;
     __syncthreads();   // the record has read the row
 
     if (ALG == AINP_SPAIN_A) {
@@ -313,62 +270,20 @@ __global__ __launch_bounds__(NT) void spain_kernel(
       }
       __syncthreads();   // the split's reads are done before the next merge
     } else {
-      // x-hat = proj(x_e + u);  u += x_e - x-hat, a lane on its own sample pairs
-#pragma unroll
-      for (int e = 0; e < SP_TPL; ++e) {
-        const int n = tid + e * NT;
-        if (n >= N || 2 * n >= w) continue;
-        const cplx c = f.ld(n);
-        const double xe[2] = {c.re * inv, c.im * inv};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int t = 2 * n + h;
-          if (t >= gs && t - gs < gl) xr[t] = xe[h] + ut[e][h];
-          ut[e][h] += xe[h] - xr[t];
-        }
-      }
-      __syncthreads();
+      sp_project_dual<NT, SP_TPL>(f, R, w, inv, ut, tid);   // x-hat = proj(x_e + u); u += x_e - x-hat
     }
-    ++cnt;
-    if (cnt % r_rate == 0) k += s_step;
+    sp_next_pass(cnt, k, s_step, r_rate);
   }
-  if (tid == 0) iters[row] = done;
-  if (hrow)
-    for (int i = done + tid; i < maxit; i += NT) hrow[i] = NAN;
-}
-
-template <int NT, int ALG, int EPL>
-static int sp_launch(const SpLds& l, double* sol, int64_t n_rows, int64_t stride,
-                     const int32_t* gap_start, const int32_t* gap_len, int w, int M, int lgN, int s,
-                     int r, double epsilon, int maxit, int32_t* iters, double* obj_history,
-                     void* stream) {
-  static const bool lds_ok =
-      hipFuncSetAttribute((const void*)spain_kernel<NT, ALG, EPL>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sp_lds(SP_WMAX, SP_MMAX).bytes()) == hipSuccess;
-  if (!lds_ok) return record_msg("ainp_spain: cannot reserve the transform's LDS");
-  hipLaunchKernelGGL((spain_kernel<NT, ALG, EPL>), dim3((unsigned)n_rows), dim3(NT), l.bytes(),
-                     as_stream(stream), sol, stride, gap_start, gap_len, w, M, lgN, s, r, epsilon,
-                     maxit, iters, obj_history, l.nF, l.nRow);
-  return check_launch("ainp_spain");
-}
-
-static bool sp_shape_ok(int w, int red) {
-  return w >= SP_WMIN && w <= SP_WMAX && (w & (w - 1)) == 0 && (red == 1 || red == 2 || red == 4) &&
-         (int64_t)red * w <= SP_MMAX;
+  sp_row_close<NT>(iters, hrow, nullptr, done, maxit, tid);
 }
 
 }  // namespace ainp
 
 using namespace ainp;
 
-extern "C" size_t ainp_spain_workspace(int64_t n_rows, int w, int red, int algorithm) {
+extern "C" size_t ainp_spain_workspace(int64_t, int, int, int) {
   // the transform, the iterate and the twiddles fit LDS over the whole
   // supported range and the spectra stay in registers: no global scratch
-  (void)n_rows;
-  (void)w;
-  (void)red;
-  (void)algorithm;
   return 0;
 }
 
@@ -376,30 +291,22 @@ extern "C" int ainp_spain(double* sol, int64_t n_rows, int64_t stride, const int
                           const int32_t* gap_len, int w, int red, int algorithm, int s, int r,
                           double epsilon, int maxit, int32_t* iters, double* obj_history,
                           void* workspace, size_t ws_bytes, void* stream) {
-  if (!sol || !gap_start || !gap_len || !iters || n_rows < 0)
-    return record_msg("ainp_spain: bad argument");
-  if (algorithm != AINP_SPAIN_A && algorithm != AINP_SPAIN_S)
-    return record_msg("ainp_spain: bad argument (algorithm is AINP_SPAIN_A or AINP_SPAIN_S)");
-  if (!sp_shape_ok(w, red))
-    return record_msg("ainp_spain: bad argument (w a power of two, 8 <= w <= 4096, red 1, 2 or 4, "
-                      "red * w <= 8192)");
-  if (stride < w) return record_msg("ainp_spain: bad argument (stride >= w)");
-  const int M = red * w;
-  if (s < 1 || r < 1) return record_msg("ainp_spain: bad argument (s >= 1, r >= 1)");
-  if (maxit < 1 || maxit > M / 2 + 1)
-    return record_msg("ainp_spain: bad argument (1 <= maxit <= red * w / 2 + 1)");
-  if (!(epsilon >= 0.0)) return record_msg("ainp_spain: bad argument (epsilon >= 0)");
+  if (int rc = sp_check_window_args(
+          "ainp_spain", sol && gap_start && gap_len && iters, n_rows, stride, w, red,
+          algorithm == AINP_SPAIN_A || algorithm == AINP_SPAIN_S, s, r, epsilon, maxit))
+    return rc;
   if (ws_bytes < ainp_spain_workspace(n_rows, w, red, algorithm) || (ws_bytes && !workspace))
     return record_msg("ainp_spain: workspace too small");
   if (n_rows > 0x7fffffff) return record_msg("ainp_spain: too many rows");
   if (n_rows == 0) return AINP_OK;
-  int lgN = 0;
-  while ((2 << lgN) < M) ++lgN;   // N = M / 2 = 1 << lgN
-  const SpLds l = sp_lds(w, M);
-#define SP_GO(NT, ALG, EPL)                                                                  \
-  return sp_launch<NT, ALG, EPL>(l, sol, n_rows, stride, gap_start, gap_len, w, M, lgN, s, r,   \
-                                 epsilon, maxit, iters, obj_history, stream)
-  if (M / 2 <= SP_NMAX_256) {
+  const int M = red * w;
+  const SpLds l = sp_window_lds(w, M, false);
+#define SP_GO(NT, ALG, EPL)                                                                     \
+  return sp_launch_rows<spain_kernel<NT, ALG, EPL>, NT>(                                        \
+      "ainp_spain", sp_window_lds(SP_WMAX, SP_MMAX, false).bytes(), l.bytes(), n_rows, stream,  \
+      sol, stride, gap_start, gap_len, w, M, sp_lgN(M), s, r, epsilon, maxit, iters,            \
+      obj_history, l.nF, l.nRow)
+  if (sp_lanes_256(M)) {
     if (algorithm == AINP_SPAIN_A) SP_GO(256, AINP_SPAIN_A, 2);
     SP_GO(256, AINP_SPAIN_S, 2);
   }

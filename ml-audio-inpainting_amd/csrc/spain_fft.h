@@ -1,8 +1,9 @@
-// spain_fft.h — what the SPAIN kernels share (spain.hip, spain_learned.hip):
-// the length-M real transform as an M/2-point complex transform on split,
-// skewed re / im arrays in LDS with quarter-wave twiddles, the slots a lane
-// holds of a half spectrum, the fixed-order workgroup sum and the radix select.
-// spain.hip's header describes the scheme.
+// spain_fft.h — what the SPAIN kernels share (spain.hip, spain_omp.hip,
+// spain_learned.hip; basis_learn.hip takes the sum): the length-M real
+// transform as an M/2-point complex transform on split, skewed re / im arrays
+// in LDS with quarter-wave twiddles, the slots a lane holds of a half spectrum,
+// the fixed-order workgroup sum and the radix select with its tie rule.
+// spain.hip's header describes the scheme; spain_plan.h sizes the arrays.
 #pragma once
 #include "common.h"
 
@@ -21,6 +22,12 @@ __device__ __forceinline__ cplx cmulc(cplx a, cplx b) {   // a * conj(b)
 }
 __device__ __forceinline__ double cabs2(cplx a) { return a.re * a.re + a.im * a.im; }
 __device__ __forceinline__ int sp_pad(int i) { return i + (i >> 5); }
+
+// The quarter wave ct[j] = cos(2 pi j / M), j <= M/4; no barrier.
+template <int NT>
+__device__ __forceinline__ void sp_quarter_wave(double* ct, int M, int tid) {
+  for (int j = tid; j <= M / 4; j += NT) ct[j] = cospi((double)(2 * j) / (double)M);
+}
 
 // exp(-2 pi i idx / M), 0 <= idx < M/2, from the quarter wave ct[0 .. M/4]
 __device__ __forceinline__ cplx sp_tw(const double* ct, int idx, int M) {
@@ -234,6 +241,41 @@ __device__ void sp_select(const uint64_t (&key)[NK], const bool (&member)[NK], i
   }
   out_shift = shift;
   need = remaining;
+}
+
+// keep[i]: key[i] is among the k largest of the `count` keys with member[i].
+// Equal keys kept only in part go to the lower bin[i], by a second select over
+// the bins of the members on the cut.  k >= count keeps all, without a barrier.
+template <int NT, int NK>
+__device__ __forceinline__ void sp_keep_largest(const uint64_t (&key)[NK], const bool (&member)[NK],
+                                                const int (&bin)[NK], int k, int count,
+                                                uint32_t* hist, int* sel, int tid,
+                                                bool (&keep)[NK]) {
+  if (k >= count) {
+#pragma unroll
+    for (int i = 0; i < NK; ++i) keep[i] = member[i];
+    return;
+  }
+  uint64_t prefix, prefix2 = 0;
+  int shift, need, have, shift2 = 0;
+  sp_select<NT, NK>(key, member, k, 56, hist, sel, tid, prefix, shift, need, have);
+  const bool tie = need < have;
+  bool member2[NK];
+  uint64_t key2[NK];
+#pragma unroll
+  for (int i = 0; i < NK; ++i) {
+    member2[i] = member[i] && (key[i] >> shift) == (prefix >> shift);
+    key2[i] = (uint64_t)(0xffff - bin[i]);
+  }
+  if (tie) {
+    int need2, have2;
+    sp_select<NT, NK>(key2, member2, need, 8, hist, sel, tid, prefix2, shift2, need2, have2);
+  }
+#pragma unroll
+  for (int i = 0; i < NK; ++i) {
+    const bool above = member[i] && (key[i] >> shift) > (prefix >> shift);
+    keep[i] = above || (member2[i] && (!tie || (key2[i] >> shift2) >= (prefix2 >> shift2)));
+  }
 }
 
 }  // namespace ainp

@@ -39,17 +39,15 @@
 // quarter wave 514 x 8 = 4112: 21 KiB.  sl_gemm: 2 x 16 x 33 x 16 = 16.5 KiB.
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "common.h"
 #include "spain_fft.h"
+#include "spain_plan.h"
 
 namespace ainp {
 
-constexpr int SL_MMIN = 8, SL_MMAX = 2048, SL_WMIN = 8;
-constexpr int64_t SL_LMAX = (int64_t)1 << 22;   // the frame cap is SL_LMAX / a frames a signal
 constexpr int SL_MAXIT = 65536;
 constexpr int SL_NT = 256;
 constexpr int SL_EPL = SL_MMAX / 4 / SL_NT;               // spectrum slots a lane: 2
@@ -136,7 +134,7 @@ __global__ __launch_bounds__(SL_NT) void sl_forward(const double* __restrict__ x
   double* re = reinterpret_cast<double*>(smem);
   double* im = re + nF;
   double* ct = im + nF;
-  for (int j = tid; j <= M / 4; j += SL_NT) ct[j] = cospi((double)(2 * j) / (double)M);
+  sp_quarter_wave<SL_NT>(ct, M, tid);
   const SpFft f = {re, im, ct, Nh, lgN, M};
   const double* xs = xc + sig * L;
   const double* us = u ? u + sig * L : nullptr;
@@ -187,7 +185,7 @@ __global__ __launch_bounds__(SL_NT) void sl_inverse(const cplx* __restrict__ Y,
   double* re = reinterpret_cast<double*>(smem);
   double* im = re + nF;
   double* ct = im + nF;
-  for (int j = tid; j <= M / 4; j += SL_NT) ct[j] = cospi((double)(2 * j) / (double)M);
+  sp_quarter_wave<SL_NT>(ct, M, tid);
   const SpFft f = {re, im, ct, Nh, lgN, M};
   const cplx* y = Y + frame * (int64_t)(Nh + 1);
   SpSpec<SL_EPL> X;
@@ -312,9 +310,10 @@ __global__ __launch_bounds__(SL_NT) __attribute__((amdgpu_waves_per_eu(1, 4))) v
   cplx zv[SL_NK], uv[SL_NK], vv[SL_NK];
   uint64_t key[SL_NK];
   bool member[SL_NK], keep[SL_NK];
+  int row[SL_NK];
 #pragma unroll
   for (int e = 0; e < SL_NK; ++e) {
-    const int bin = tid + e * SL_NT;
+    const int bin = row[e] = tid + e * SL_NT;
     member[e] = bin < K;
     zv[e] = uv[e] = vv[e] = zero;
     double m2 = 0.0;
@@ -331,32 +330,7 @@ __global__ __launch_bounds__(SL_NT) __attribute__((amdgpu_waves_per_eu(1, 4))) v
     }
     key[e] = (uint64_t)__double_as_longlong(m2);
   }
-  if (k >= K) {
-#pragma unroll
-    for (int e = 0; e < SL_NK; ++e) keep[e] = member[e];
-  } else {
-    uint64_t prefix, prefix2 = 0;
-    int shift, need, have, shift2 = 0;
-    sp_select<SL_NT, SL_NK>(key, member, k, 56, hist, sel, tid, prefix, shift, need, have);
-    const bool tie = need < have;   // equal magnitudes, kept in part: lower rows first
-    bool member2[SL_NK];
-    uint64_t key2[SL_NK];
-#pragma unroll
-    for (int e = 0; e < SL_NK; ++e) {
-      member2[e] = member[e] && (key[e] >> shift) == (prefix >> shift);
-      key2[e] = (uint64_t)(0xffff - (tid + e * SL_NT));
-    }
-    if (tie) {
-      int need2, have2;
-      sp_select<SL_NT, SL_NK>(key2, member2, need, 8, hist, sel, tid, prefix2, shift2, need2,
-                              have2);
-    }
-#pragma unroll
-    for (int e = 0; e < SL_NK; ++e) {
-      const bool above = member[e] && (key[e] >> shift) > (prefix >> shift);
-      keep[e] = above || (member2[e] && (!tie || (key2[e] >> shift2) >= (prefix2 >> shift2)));
-    }
-  }
+  sp_keep_largest<SL_NT, SL_NK>(key, member, row, k, K, hist, sel, tid, keep);
   double acc = 0.0;
 #pragma unroll
   for (int e = 0; e < SL_NK; ++e) {
@@ -468,22 +442,6 @@ __global__ __launch_bounds__(SL_NT) void sl_decide(const double* __restrict__ pa
   if (obj <= epsilon || cnt == maxit) done[sig] = 1;
 }
 
-static bool sl_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
-
-// the first rule (w, a, M, L) breaks, or nullptr
-static const char* sl_shape_rule(int64_t L, int w, int a, int M) {
-  if (!sl_pow2(M) || M < SL_MMIN || M > SL_MMAX)
-    return "ainp_spain_learned: bad argument (M a power of two, 8 <= M <= 2048)";
-  if (!sl_pow2(w) || w < SL_WMIN || w > M)
-    return "ainp_spain_learned: bad argument (w a power of two, 8 <= w <= M)";
-  if (a < 1 || w % a != 0 || w / a < 2)
-    return "ainp_spain_learned: bad argument (a divides w, w / a >= 2)";
-  if (L < M || L % M != 0) return "ainp_spain_learned: bad argument (L a positive multiple of M)";
-  if (L > SL_LMAX)
-    return "ainp_spain_learned: bad argument (L / a <= 2^22 / a frames, L <= 4194304)";
-  return nullptr;
-}
-
 }  // namespace ainp
 
 using namespace ainp;
@@ -501,16 +459,14 @@ extern "C" int ainp_spain_learned(double* x, const uint8_t* observed, int64_t L,
                                   int r, double epsilon, int maxit, int32_t* iters,
                                   double* obj_history, void* workspace, size_t ws_bytes,
                                   void* stream) {
-  if (!x || !observed || !iters || n_signals < 0)
-    return record_msg("ainp_spain_learned: bad argument");
+  const char* fn = "ainp_spain_learned";
+  if (!x || !observed || !iters || n_signals < 0) return record_bad_argument(fn);
   if (algorithm != AINP_SPAIN_A && algorithm != AINP_SPAIN_S)
-    return record_msg("ainp_spain_learned: bad argument (algorithm is AINP_SPAIN_A or "
-                      "AINP_SPAIN_S)");
-  if (const char* rule = sl_shape_rule(L, w, a, M)) return record_msg(rule);
-  if (s < 1 || r < 1) return record_msg("ainp_spain_learned: bad argument (s >= 1, r >= 1)");
-  if (!(epsilon >= 0.0)) return record_msg("ainp_spain_learned: bad argument (epsilon >= 0)");
-  if (maxit < 1 || maxit > SL_MAXIT)
-    return record_msg("ainp_spain_learned: bad argument (1 <= maxit <= 65536)");
+    return record_bad_argument(fn, "algorithm is AINP_SPAIN_A or AINP_SPAIN_S");
+  if (const char* rule = sl_shape_rule(L, w, a, M)) return record_bad_argument(fn, rule);
+  if (s < 1 || r < 1) return record_bad_argument(fn, "s >= 1, r >= 1");
+  if (!(epsilon >= 0.0)) return record_bad_argument(fn, "epsilon >= 0");
+  if (maxit < 1 || maxit > SL_MAXIT) return record_bad_argument(fn, "1 <= maxit <= 65536");
   const int64_t N = L / a, nblk = cdiv(L, SL_NT);
   if (n_signals * std::max(N, nblk) > 0x7fffffff)
     return record_msg("ainp_spain_learned: too many signals (n_signals L / a < 2^31)");
@@ -532,10 +488,8 @@ extern "C" int ainp_spain_learned(double* x, const uint8_t* observed, int64_t L,
   const cplx* U = reinterpret_cast<const cplx*>(basis);
   const int K = M / 2 + 1;
   const int64_t NF = n_signals * N, total = n_signals * L;
-  int lgN = 0;
-  while ((2 << lgN) < M) ++lgN;   // M / 2 = 1 << lgN
-  const int nF = M / 2 + M / 64 + 2, nCos = (M / 4 + 2) & ~1;
-  const size_t lds = ((size_t)2 * nF + nCos) * sizeof(double);
+  const int lgN = sp_lgN(M), nF = sp_fft_lds(M).nF;
+  const size_t lds = sp_fft_lds(M).bytes();
   const dim3 gFrames((unsigned)NF), gSamples((unsigned)(n_signals * nblk)), nt(SL_NT);
   const dim3 gGemm((unsigned)cdiv(NF, SL_TILE), (unsigned)cdiv(K, SL_TILE));
   const bool isA = algorithm == AINP_SPAIN_A;
@@ -619,12 +573,8 @@ extern "C" size_t ainp_spain_dgt_workspace(int64_t n_signals, int w) {
 
 extern "C" int ainp_spain_dgt(const double* x, int64_t L, int64_t n_signals, int w, int a, int M,
                               double* coef, void* workspace, size_t ws_bytes, void* stream) {
-  if (!x || !coef || n_signals < 0) return record_msg("ainp_spain_dgt: bad argument");
-  if (const char* rule = sl_shape_rule(L, w, a, M)) {
-    char msg[256];
-    snprintf(msg, sizeof(msg), "ainp_spain_dgt%s", rule + sizeof("ainp_spain_learned") - 1);
-    return record_msg(msg);
-  }
+  if (!x || !coef || n_signals < 0) return record_bad_argument("ainp_spain_dgt");
+  if (const char* rule = sl_shape_rule(L, w, a, M)) return record_bad_argument("ainp_spain_dgt", rule);
   const int64_t N = L / a, NF = n_signals * N;
   if (NF > 0x7fffffff) return record_msg("ainp_spain_dgt: too many signals (n_signals L / a < 2^31)");
   if (n_signals == 0) return AINP_OK;
@@ -637,12 +587,10 @@ extern "C" int ainp_spain_dgt(const double* x, int64_t L, int64_t n_signals, int
                                      dgt_ws_bytes(n_signals, w) - sizeof(int) * (size_t)n_signals);
   hipError_t e = hipMemsetAsync(done, 0, sizeof(int) * (size_t)n_signals, st);
   if (e != hipSuccess) return record_error(e, "ainp_spain_dgt");
-  int lgN = 0;
-  while ((2 << lgN) < M) ++lgN;   // M / 2 = 1 << lgN
-  const int nF = M / 2 + M / 64 + 2, nCos = (M / 4 + 2) & ~1;
-  const size_t lds = ((size_t)2 * nF + nCos) * sizeof(double);
+  const SpLds l = sp_fft_lds(M);
   hipLaunchKernelGGL(sl_windows, dim3(1), dim3(SL_NT), 0, st, g, gd, w, a, M);
-  hipLaunchKernelGGL(sl_forward, dim3((unsigned)NF), dim3(SL_NT), lds, st, x, (const double*)nullptr,
-                     g, reinterpret_cast<cplx*>(coef), L, (int)N, w, a, M, lgN, nF, done);
+  hipLaunchKernelGGL(sl_forward, dim3((unsigned)NF), dim3(SL_NT), l.bytes(), st, x,
+                     (const double*)nullptr, g, reinterpret_cast<cplx*>(coef), L, (int)N, w, a, M,
+                     sp_lgN(M), l.nF, done);
   return check_launch("ainp_spain_dgt");
 }

@@ -4,13 +4,14 @@
 //
 // The loop is spain.hip's S-SPAIN with z-bar = OMP_k(x-hat - u) in place of
 // H_k(A (x-hat - u)); frame, objective, record, stop, projection, dual update
-// and k schedule are the same, and so are the transforms, the slots and the
-// fixed-order sum (spain_fft.h).  OMP_k(v) is greedy least squares over the
-// atoms d_m[i] = exp(2 pi i m i / M) / sqrt(M), i < w: while the residual is
-// above tol = 10^(errdb / 20) |v| and fewer than k atoms are chosen, take the
-// unselected half-spectrum bin with the largest |(A r)_m| (plain magnitudes,
-// ties to the lower bin) and solve min |v - A* z| over conjugate-symmetric z on
-// the chosen bins and their mirrors.
+// and k schedule are the same; record, schedule, the row rule, load and closing
+// are the same code (spain_window.h), and so are the transforms,
+// the slots and the fixed-order sum (spain_fft.h).  OMP_k(v) is greedy least
+// squares over the atoms d_m[i] = exp(2 pi i m i / M) / sqrt(M), i < w: while
+// the residual is above tol = 10^(errdb / 20) |v| and fewer than k atoms are
+// chosen, take the unselected half-spectrum bin with the largest |(A r)_m|
+// (plain magnitudes, ties to the lower bin) and solve min |v - A* z| over
+// conjugate-symmetric z on the chosen bins and their mirrors.
 //
 // The least squares runs in coefficient space over real columns: an atom m
 // other than DC and Nyquist brings R_m = 2 Re d_m and I_m = -2 Im d_m with the
@@ -44,39 +45,16 @@
 #include <algorithm>
 #include <cmath>
 
-#include "ar_limits.h"
-#include "common.h"
-#include "spain_fft.h"
+#include "spain_window.h"
 
 namespace ainp {
 
-constexpr int SO_WMIN = 8, SO_WMAX = 4096, SO_MMAX = 8192;   // spain.hip's range
-constexpr int SO_NMAX_256 = 1024;   // the longest transform the 256-lane kernel takes (2 slots)
-constexpr int SO_NT_BIG = 512, SO_EPL_BIG = 2048 / SO_NT_BIG;
 constexpr double SO_PIVOT = 1e-10;  // smallest relative squared pivot of a new column
 
 enum { SO_R = 0, SO_I = 1, SO_S = 2 };   // 2 Re d_m, -2 Im d_m, d_m (DC, Nyquist)
 
-struct SoLds {
-  int nF, nRow, nCos, nD, nA;   // doubles: re / im, the row, the quarter wave, a vector; atoms
-  size_t bytes() const {
-    return ((size_t)2 * nF + nRow + nCos + 4 * nD) * sizeof(double) +
-           ((size_t)nD + 2 * nA) * sizeof(int);
-  }
-};
-static int so_dims(int w) { return std::min(w, AINP_SPAIN_OMP_DIMS); }
-static SoLds so_lds(int w, int M) {
-  SoLds l;
-  const int N = M / 2;
-  l.nF = N + N / 32 + 2;
-  l.nRow = w;
-  l.nCos = (M / 4 + 2) & ~1;
-  l.nD = so_dims(w);
-  l.nA = l.nD / 2 + 2;
-  return l;
-}
 static size_t so_tsize(int w) {   // doubles of a row's packed T
-  const size_t d = (size_t)so_dims(w);
+  const size_t d = (size_t)sp_omp_dims(w);
   return d * (d + 1) / 2;
 }
 
@@ -211,19 +189,12 @@ __global__ __launch_bounds__(NT) void spain_omp_kernel(
   const int gs = gap_start[row], gl = gap_len[row];
   double* hrow = obj_history ? obj_history + row * maxit : nullptr;
   int32_t* arow = n_atoms ? n_atoms + row * maxit : nullptr;
-  // a row whose run does not lie in the window is left alone
-  if (gs < 0 || gl < 1 || gl > JN_HMAX || (int64_t)gs + gl > w) {
-    if (tid == 0) iters[row] = 0;
-    for (int i = tid; i < maxit; i += NT) {
-      if (hrow) hrow[i] = NAN;
-      if (arow) arow[i] = -1;
-    }
+  if (!sp_run_ok(gs, gl, w)) {
+    sp_row_close<NT>(iters, hrow, arow, 0, maxit, tid);
     return;
   }
-  double* x = sol + row * stride;
-  for (int j = tid; j <= M / 4; j += NT) ct[j] = cospi((double)(2 * j) / (double)M);
-  for (int i = tid; i < w; i += NT) xr[i] = (i >= gs && i - gs < gl) ? 0.0 : x[i];
-  __syncthreads();
+  const SpRow R = {xr, sol + row * stride, hrow, arow, gs, gl};
+  sp_row_load<NT>(R, ct, w, M, tid);
 
   const SpFft f = {re, im, ct, N, lgN, M};
   const double fwd = 1.0 / sqrt((double)M);   // analysis: FFT_M / sqrt(M)
@@ -405,17 +376,8 @@ __global__ __launch_bounds__(NT) void spain_omp_kernel(
     }
     const double obj = sqrt(sp_sum<NT>(acc, part, tid));
     done = cnt;
-    if (tid == 0) {
-      if (hrow) hrow[cnt - 1] = obj;
-      if (arow) arow[cnt - 1] = na;
-    }
-    if (obj <= best) {   // record the iterate the objective was evaluated on
-      best = obj;
-      for (int i = tid; i < gl; i += NT) x[gs + i] = xr[gs + i];
-    }
-    if (obj <= epsilon) break;
+    if (sp_record<NT>(R, obj, cnt, na, best, epsilon, tid)) break;
     __syncthreads();   // the record has read the row
-
     // x-hat = proj(x_e + u);  u += x_e - x-hat, a lane on its own sample pairs
 #pragma unroll
     for (int e = 0; e < SP_TPL; ++e) {
@@ -431,37 +393,9 @@ __global__ __launch_bounds__(NT) void spain_omp_kernel(
       }
     }
     __syncthreads();
-    ++cnt;
-    if (cnt % r_rate == 0) k += s_step;
+    sp_next_pass(cnt, k, s_step, r_rate);
   }
-  if (tid == 0) iters[row] = done;
-  for (int i = done + tid; i < maxit; i += NT) {
-    if (hrow) hrow[i] = NAN;
-    if (arow) arow[i] = -1;
-  }
-}
-
-template <int NT, int EPL>
-static int so_launch(const SoLds& l, double* sol, int64_t n_rows, int64_t stride,
-                     const int32_t* gap_start, const int32_t* gap_len, int w, int M, int lgN,
-                     int red, int s, int r, double epsilon, int maxit, double tolfac,
-                     int32_t* iters, double* obj_history, int32_t* n_atoms, double* T,
-                     void* stream) {
-  static const bool lds_ok =
-      hipFuncSetAttribute((const void*)spain_omp_kernel<NT, EPL>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)so_lds(SO_WMAX, SO_MMAX).bytes()) == hipSuccess;
-  if (!lds_ok) return record_msg("ainp_spain_omp: cannot reserve the transform's LDS");
-  hipLaunchKernelGGL((spain_omp_kernel<NT, EPL>), dim3((unsigned)n_rows), dim3(NT), l.bytes(),
-                     as_stream(stream), sol, stride, gap_start, gap_len, w, M, lgN, red, s, r,
-                     epsilon, maxit, tolfac, iters, obj_history, n_atoms, T,
-                     (int64_t)so_tsize(w), l.nF, l.nRow, l.nCos, l.nD, l.nA);
-  return check_launch("ainp_spain_omp");
-}
-
-static bool so_shape_ok(int w, int red) {
-  return w >= SO_WMIN && w <= SO_WMAX && (w & (w - 1)) == 0 && (red == 1 || red == 2 || red == 4) &&
-         (int64_t)red * w <= SO_MMAX;
+  sp_row_close<NT>(iters, hrow, arow, done, maxit, tid);
 }
 
 }  // namespace ainp
@@ -469,7 +403,7 @@ static bool so_shape_ok(int w, int red) {
 using namespace ainp;
 
 extern "C" size_t ainp_spain_omp_workspace(int64_t n_rows, int w, int red) {
-  if (n_rows < 0 || !so_shape_ok(w, red)) return 0;
+  if (n_rows < 0 || !sp_shape_ok(w, red)) return 0;
   return (size_t)n_rows * so_tsize(w) * sizeof(double);
 }
 
@@ -478,37 +412,30 @@ extern "C" int ainp_spain_omp(double* sol, int64_t n_rows, int64_t stride,
                               int s, int r, double epsilon, int maxit, double errdb,
                               int32_t* iters, double* obj_history, int32_t* n_atoms,
                               void* workspace, size_t ws_bytes, void* stream) {
-  if (!sol || !gap_start || !gap_len || !iters || n_rows < 0)
-    return record_msg("ainp_spain_omp: bad argument");
-  if (!so_shape_ok(w, red))
-    return record_msg("ainp_spain_omp: bad argument (w a power of two, 8 <= w <= 4096, red 1, 2 "
-                      "or 4, red * w <= 8192)");
-  if (stride < w) return record_msg("ainp_spain_omp: bad argument (stride >= w)");
-  const int M = red * w;
-  if (s < 1 || r < 1) return record_msg("ainp_spain_omp: bad argument (s >= 1, r >= 1)");
-  if (maxit < 1 || maxit > M / 2 + 1)
-    return record_msg("ainp_spain_omp: bad argument (1 <= maxit <= red * w / 2 + 1)");
-  if (!(epsilon >= 0.0)) return record_msg("ainp_spain_omp: bad argument (epsilon >= 0)");
-  if (!(errdb >= -300.0 && errdb <= 0.0))
-    return record_msg("ainp_spain_omp: bad argument (-300 <= errdb <= 0)");
+  const char* fn = "ainp_spain_omp";
+  if (int rc = sp_check_window_args(fn, sol && gap_start && gap_len && iters, n_rows, stride, w, red,
+                                    true, s, r, epsilon, maxit))
+    return rc;
+  if (!(errdb >= -300.0 && errdb <= 0.0)) return record_bad_argument(fn, "-300 <= errdb <= 0");
   // the largest k of the schedule: k(cnt) = s (1 + cnt / r - 1 / r)
   const int64_t kmax = (int64_t)s * (1 + maxit / r - 1 / r);
   if (std::min<int64_t>(2 * kmax, w) > AINP_SPAIN_OMP_DIMS)
-    return record_msg("ainp_spain_omp: bad argument (min(2 k(maxit), w) <= 512 real unknowns, "
-                      "k(maxit) = s (1 + maxit / r - 1 / r))");
+    return record_bad_argument(fn, "min(2 k(maxit), w) <= 512 real unknowns, "
+                               "k(maxit) = s (1 + maxit / r - 1 / r)");
   if (n_rows > 0x7fffffff) return record_msg("ainp_spain_omp: too many rows");
   if (ws_bytes < ainp_spain_omp_workspace(n_rows, w, red) || (n_rows && !workspace))
     return record_msg("ainp_spain_omp: workspace too small");
   if (n_rows == 0) return AINP_OK;
-  int lgN = 0;
-  while ((2 << lgN) < M) ++lgN;   // N = M / 2 = 1 << lgN
-  const SoLds l = so_lds(w, M);
+  const int M = red * w;
+  const SpLds l = sp_window_lds(w, M, true);
   const double tolfac = pow(10.0, errdb / 20.0);
 #define SO_GO(NT, EPL)                                                                          \
-  return so_launch<NT, EPL>(l, sol, n_rows, stride, gap_start, gap_len, w, M, lgN, red, s, r,   \
-                            epsilon, maxit, tolfac, iters, obj_history, n_atoms,                \
-                            static_cast<double*>(workspace), stream)
-  if (M / 2 <= SO_NMAX_256) SO_GO(256, 2);
-  SO_GO(SO_NT_BIG, SO_EPL_BIG);
+  return sp_launch_rows<spain_omp_kernel<NT, EPL>, NT>(                                         \
+      fn, sp_window_lds(SP_WMAX, SP_MMAX, true).bytes(), l.bytes(), n_rows, stream, sol,        \
+      stride, gap_start, gap_len, w, M, sp_lgN(M), red, s, r, epsilon, maxit, tolfac, iters,    \
+      obj_history, n_atoms, static_cast<double*>(workspace), (int64_t)so_tsize(w), l.nF,        \
+      l.nRow, l.nCos, l.nD, l.nA)
+  if (sp_lanes_256(M)) SO_GO(256, 2);
+  SO_GO(SP_NT_BIG, SP_EPL_BIG);
 #undef SO_GO
 }

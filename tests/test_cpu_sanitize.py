@@ -19,7 +19,10 @@ libainp_torch_ubsan.so; test_gpu_sanitize.py runs it on the GPU box.
   tests/sanitize/conv_gen_route_check.cpp, likewise.
 
   csrc/gemm_route.h (the GEMM launchers' split-K cover rule and the tile
-  ainp_gemm_bf16nt takes): tests/sanitize/gemm_route_check.cpp, likewise."""
+  ainp_gemm_bf16nt takes): tests/sanitize/gemm_route_check.cpp, likewise.
+
+  csrc/spain_plan.h (the SPAIN launchers' shape rules, LDS plans and lane
+  route): tests/sanitize/spain_plan_check.cpp, likewise."""
 import glob
 import os
 import subprocess
@@ -143,3 +146,19 @@ def test_gemm_route_under_asan_ubsan(sanitize_build):
     assert model["gemm16_256=1", "g256_bk64=1"]["proj"] == "g256::gemm_bf16nt_256b_kernel"
     assert model["gemm16_256=0", "g256_bk64=0"]["proj"] == g16
     assert model["gemm16_256=0", "g256_bk64=1"]["proj"] == g16
+
+
+def test_spain_plan_under_asan_ubsan(sanitize_build):
+    """Over every legal (w, red) of the window solvers, every legal M of the
+    whole-signal solver and their neighbours outside: the plan's sizes, lgN and
+    lane route equal the launchers' former expressions, the shape rules refuse
+    what they refused with the former messages, and every LDS plan fits a CU."""
+    exe = os.path.join(os.path.dirname(sanitize_build), "spain_plan_check")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    env.pop("LD_PRELOAD", None)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-3000:]
+    assert "spain_plan_check OK" in out
+    assert "runtime error" not in out and "AddressSanitizer" not in out, out[-3000:]
