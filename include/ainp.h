@@ -708,8 +708,11 @@ int ainp_conv3x3_wgrad(const float* x, const float* in_scale,
 #define AINP_CONV_X16 8
 #define AINP_CONV_Y16 16
 /* Round 5: channel-last activations, [N][H][W][C] (a pixel's channels
- * contiguous; 1-2-channel tensors are the same in either layout).  The
- * input (forward: x; data gradient: dy; weight gradient: x) is channel-last
+ * contiguous).  The flags act on tensors of 16 channels and more: the 1- or
+ * 2-channel side of the small pairs (1 / 2 <-> 16) is planar [N][C][H][W]
+ * with or without its flag (one channel: the two layouts coincide; two
+ * channels: the planes are NOT interleaved).  The input
+ * (forward: x; data gradient: dy; weight gradient: x) is channel-last
  * with AINP_CONV_XCL, the output (forward: y; data gradient: dx) with
  * AINP_CONV_YCL, the weight gradient's dy with AINP_CONV_GCL.  Every
  * combination with the bf16 flags above; served for the pairs

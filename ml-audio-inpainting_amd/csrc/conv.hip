@@ -1546,8 +1546,8 @@ static void launch_small_fwd_l(bool dgrad, const float* x, const float* w, const
 }
 
 // lay (round 5): bit 0 = input channel-last (a 16-channel input), bit 1 =
-// output channel-last (a 16-channel output); 1-2-channel tensors are the
-// same in both layouts
+// output channel-last (a 16-channel output); 1-2-channel tensors stay planar
+// (include/ainp.h: the flag does not act on them)
 template <int CIN, int COUT>
 static void launch_small_fwd(bool dgrad, const float* x, const float* w, const float* bias,
                              const float* sc, const float* sh, float* y, double* stats,

@@ -290,6 +290,13 @@ inline bool x6_route(const ConvEnv& env, const ConvCall& c, ConvRoute* r) {
   const bool pers_pair = pers && ((!c.dgrad && p3264) || p1632 || p3216);
   const bool tiled_pair = (p3264 || (c.Cin == 64 && cop == 32)) && cin_fits;
   if (!pers_pair && !tiled_pair) return false;
+  // the channel-last stores write four consecutive channels of a pixel: a
+  // Cout that is no multiple of 4 would run into the next pixel (and, on the
+  // last one, past the tensor)
+  if ((c.lay & CL_Y) && c.Cout % 4 != 0) {
+    *r = refused(CR_CL16);
+    return true;
+  }
   const int occ = c.b16 ? env.x6_occ16 : 1;
   if (pers_pair) {
     // bf16 channel-last forward with bf16 source and output: the LDS-DMA
