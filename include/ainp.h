@@ -563,7 +563,8 @@ int ainp_gemm_x6nt_256(int64_t M, int64_t N, int64_t K, const float* A, int64_t 
  *   bias: (bias_a1 + bias_a2)[n] for n < bias_nsplit, (bias_b1 + bias_b2)
  *         [n - bias_nsplit] after (any may be NULL), slab 0 only
  *   nsplit > 1: split-K, split s sums k in [s*kc, min(K, (s+1)*kc)) into
- *         C + s*strideC (and C2 + s*strideC)
+ *         C + s*strideC (and C2 + s*strideC); strideC >= ldc times the rows of
+ *         a slab (M, or with C2 the larger of c_msplit and M - c_msplit)
  * Requirements: K, kc, a_ksplit, b_ksplit % 16 == 0; b_nsplit, c_msplit %
  * 256 == 0; operands 16-byte aligned with ld % 4 == 0; k-major operands have
  * a row count % 4 == 0.  Arithmetic: the exact three-piece bf16 split, six

@@ -439,9 +439,9 @@ extern "C" int ainp_gemm_x6_multi(const ainp_x6_problem* probs, int nprobs, void
     bool ok = M > 0 && N > 0 && K > 0 && K % x6r::BK == 0 && s.A && s.B && s.C &&
               a16(s.A) && a16(s.B) && s.lda % 4 == 0 && s.ldb % 4 == 0 && s.ldc >= N &&
               nsplit <= 65535;
-    // k-contiguous operands: rows of >= K floats; k-major ones: R % 4 == 0
-    const int64_t arows = (s.A2 && s.a_ksplit > 0) ? M : M;
-    ok = ok && (s.a_kmajor ? (s.lda >= arows && M % 4 == 0) : s.lda >= (s.A2 ? s.a_ksplit : K));
+    // k-contiguous operands: rows of >= K floats; k-major ones (A and A2 alike:
+    // k-rows of M floats): R % 4 == 0
+    ok = ok && (s.a_kmajor ? (s.lda >= M && M % 4 == 0) : s.lda >= (s.A2 ? s.a_ksplit : K));
     const bool bn = s.B2 && s.b_ksplit <= 0;   // B split along n
     ok = ok && (s.b_kmajor ? (s.ldb >= (bn ? s.b_nsplit : N) && N % 4 == 0 &&
                               (!bn || (N - s.b_nsplit) % 4 == 0))
@@ -452,12 +452,13 @@ extern "C" int ainp_gemm_x6_multi(const ainp_x6_problem* probs, int nprobs, void
            (s.b_ksplit > 0 ? (s.b_ksplit % x6r::BK == 0 && s.b_ksplit < K)
                            : (s.b_nsplit > 0 && s.b_nsplit % x6r::BN == 0 && s.b_nsplit < N));
     if (s.C2) ok = ok && s.c_msplit > 0 && s.c_msplit % x6r::BM == 0 && s.c_msplit < M;
-    ok = ok && splitk_covers(K, nsplit, kc, x6r::BK) &&
-         (nsplit == 1 || s.strideC >= (s.C2 ? s.c_msplit : M) * s.ldc);
+    // a slab holds the rows of C and, at the same stride, those of C2: the taller of the two
+    const int64_t slab_rows = s.C2 ? (s.c_msplit > M - s.c_msplit ? s.c_msplit : M - s.c_msplit) : M;
+    ok = ok && splitk_covers(K, nsplit, kc, x6r::BK) && (nsplit == 1 || s.strideC >= slab_rows * s.ldc);
     if (s.A2 && nsplit > 1) ok = ok && s.a_ksplit % kc == 0;   // no K-tile straddles
     if (!ok)
       return record_msg("ainp_gemm_x6_multi: bad problem (K % 16, 16-byte aligned operands, "
-                        "ld % 4, k-major rows % 4, splits on tile boundaries, split-K cover)");
+                        "ld % 4, k-major rows % 4, splits on tile boundaries, split-K cover and slab stride)");
     d.A = s.A; d.A2 = s.A2; d.lda = s.lda; d.a_ksplit = s.A2 ? s.a_ksplit : 0; d.a_km = s.a_kmajor;
     d.B = s.B; d.B2 = s.B2; d.ldb = s.ldb; d.b_nsplit = s.b_nsplit;
     d.b_ksplit = s.B2 ? s.b_ksplit : 0; d.b_km = s.b_kmajor;
