@@ -220,6 +220,42 @@ int ainp_janssen_ex(double* sol, int64_t n_segments, int64_t stride, const int32
                     size_t workspace_bytes, int method, void* stream);
 size_t ainp_janssen_ex_workspace(int64_t n_segments, int n_max, int p, int gap_max, int method);
 
+/* ainp_janssen_ex for any set of missing samples in a segment (janssen_inp.m
+ * takes any NaN pattern): several gaps, scattered samples, a gap beside another.
+ * miss_off int32 [n_segments + 1], miss_idx int32 [miss_off[n_segments]], both
+ * on the device: segment i's missing samples are miss_idx[miss_off[i] ..
+ * miss_off[i + 1]), strictly ascending, 0-based within the row, inside
+ * [0, n[i]).  h_max: the longest list (it sizes LDS and the workspace).
+ * Per iteration, with M_0 < ... < M_{h-1} the list: a and b as in ainp_janssen
+ * (method as in ainp_janssen_ex), g_i = -sum_{n observed, |M_i - n| <= p}
+ * b[|M_i - n|] x_n, then G z = g with G[i][j] = b[|M_i - M_j|] where the
+ * distance is <= p, else 0 -- symmetric positive-definite, banded by index
+ * distance, not Toeplitz: a float64 Cholesky factorisation G = L L^T, left-
+ * looking over block columns of 8 inside G's envelope (tiles wholly outside the
+ * band are skipped, G is never formed), then the two substitutions.  A pivot
+ * that is not positive and finite, or a z that is not finite, stops the segment
+ * and the previous iterate stays (the reference's chol break, the rule of
+ * ainp_janssen).  One workgroup per segment for all iterations, no atomics,
+ * every sum in a fixed order: the same bits on every call, and history[i][k]
+ * equals a run with maxit = k + 1.
+ * history (nullable) [n_segments][maxit][hist_row], hist_row >= h_max: the
+ * missing samples in list order after each completed iteration; other entries
+ * are not written.  iters_done as for ainp_janssen: iterations completed, 0 for
+ * a silent context or a failed first fit, 0 with nothing written for an empty
+ * list, -1 (row untouched) for a row outside the supported range -- a list that
+ * is out of order or out of the row counts as such.
+ * Supported: 1 <= p <= 3072, p < n[i] <= min(stride, 16384), 1 <= h <= h_max <=
+ * 2048, 1 <= maxit <= 1000.  workspace (device): at least
+ * ainp_janssen_mask_workspace(n_segments, min(stride, 16384), p, h_max, method)
+ * bytes; per segment, in doubles: the row with its missing samples zeroed
+ * (n_max rounded up to even), then L by columns as a band, h_max rounded up to
+ * even columns of min(h_max - 1, p) + 1 entries (L[i][k] at k (bw + 1) + i - k). */
+size_t ainp_janssen_mask_workspace(int64_t n_segments, int n_max, int p, int h_max, int method);
+int ainp_janssen_mask(double* sol, int64_t n_segments, int64_t stride, const int32_t* n,
+                      const int32_t* miss_off, const int32_t* miss_idx, int h_max, int p,
+                      int maxit, int method, double* history, int64_t hist_row,
+                      int32_t* iters_done, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Forward/backward AR extrapolation of one gap per segment, the `extrapolation`
  * row of the same comparison (models/AudioReg/utils/arinpaint.m).  Float64.
  * sol, n, gap_start, gap_len as for ainp_janssen; the gap's content on entry is

@@ -256,6 +256,10 @@ _SIGS = {
     "ainp_janssen_ex": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, P, P, P, c_size_t,
                                 c_int, P]),
     "ainp_janssen_ex_workspace": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    # the same for any set of missing samples (csrc/janssen_mask.hip)
+    "ainp_janssen_mask": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, c_int, c_int, P,
+                                  c_int64, P, P, c_size_t, P]),
+    "ainp_janssen_mask_workspace": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
     # forward/backward AR extrapolation (csrc/ar_extrapolate.hip)
     "ainp_ar_extrapolate": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, c_int, P, P,
                                     c_size_t, P]),

@@ -5,7 +5,9 @@ method "lpc" or "arburg").
 train.m cuts one segment of w samples either side of every gap and hands each
 to janssen_inp; here every gap of every signal becomes one row of a batch and
 the whole batch is one launch of ainp_janssen_ex (csrc/janssen.hip, float64)
-or of ainp_ar_extrapolate (csrc/ar_extrapolate.hip).
+or of ainp_ar_extrapolate (csrc/ar_extrapolate.hip).  janssen_inpaint_mask lifts
+the one-gap-per-segment limit: gaps closer than w share a segment, solved by
+ainp_janssen_mask (csrc/janssen_mask.hip), as janssen_inp.m takes any mask.
 Segments are clipped to the signal (train.m:134-135 indexes past the ends for
 a gap within w of them).  gap_sdr is train.m:196 / model_eval.m:60.
 
@@ -81,6 +83,61 @@ def plan_segments(masks, w=4096, p=512):
     return Segments(*(c.astype(np.int32) for c in cols))
 
 
+@dataclass
+class MaskSegments:
+    """One row per cluster of runs: signal index, segment [lo, lo + n) within
+    it, the missing samples relative to lo (ascending), and how many runs they
+    form."""
+    signal: np.ndarray
+    lo: np.ndarray
+    n: np.ndarray
+    missing: list
+    runs: np.ndarray
+
+    def __len__(self):
+        return len(self.signal)
+
+
+def plan_mask_segments(masks, w=4096, p=512):
+    """The batch layout for any mask: consecutive runs of missing samples
+    [a_k, b_k), [a_k+1, b_k+1) share a cluster exactly when a_k+1 - b_k < w (where
+    plan_segments refuses), and a cluster's segment is [a_first - w, b_last + w)
+    clipped to its signal.  Where nothing merges the rows are plan_segments'.
+    ValueError for what the kernel does not cover: more than 2048 missing
+    samples in a cluster, a segment longer than 16384 or not longer than p."""
+    if w < 1:
+        raise ValueError("w must be positive")
+    sig, los, ns, miss, runs = [], [], [], [], []
+    for i, obs in enumerate(masks):
+        clusters = []
+        for a, b in find_gaps(obs):
+            if clusters and a - clusters[-1][-1][1] < w:
+                clusters[-1].append((a, b))
+            else:
+                clusters.append([(a, b)])
+        for cl in clusters:
+            a, b = cl[0][0], cl[-1][1]
+            count = sum(e - s for s, e in cl)
+            if count > GAP_MAX:
+                raise ValueError(f"signal {i}: the gaps in [{a}, {b}) hold {count} missing "
+                                 f"samples, at most {GAP_MAX} per segment")
+            lo, hi = max(0, a - w), min(len(obs), b + w)
+            if hi - lo > N_MAX:
+                raise ValueError(f"signal {i}: segment [{lo}, {hi}) of {hi - lo} samples, at "
+                                 f"most {N_MAX}")
+            if hi - lo <= p:
+                raise ValueError(f"signal {i}: segment [{lo}, {hi}) of {hi - lo} samples needs "
+                                 f"p < {hi - lo}")
+            sig.append(i)
+            los.append(lo)
+            ns.append(hi - lo)
+            miss.append(np.concatenate([np.arange(s - lo, e - lo, dtype=np.int32)
+                                        for s, e in cl]))
+            runs.append(len(cl))
+    return MaskSegments(np.array(sig, np.int32), np.array(los, np.int32), np.array(ns, np.int32),
+                        miss, np.array(runs, np.int32))
+
+
 def check_args(p, maxit):
     if not 1 <= int(p) <= P_MAX:
         raise ValueError(f"p must be in [1, {P_MAX}]")
@@ -137,6 +194,65 @@ def janssen_inpaint(signal, mask=None, p=512, w=4096, maxit=20, return_history=F
                                 return_history=return_history, method=method))
     for r, d in enumerate(info):
         d["history"] = hist[r, :, :int(seg.gap_len[r])].copy() if hist is not None else None
+    out = restack(sigs, kind)
+    return (out, info) if return_history else out
+
+
+def janssen_inpaint_mask(signal, mask=None, p=512, w=4096, maxit=20, return_history=False,
+                         device="cuda", method="lpc"):
+    """janssen_inpaint for any mask: gaps closer than w to one another share a
+    segment and are solved together, as the reference's janssen_inp.m does with
+    any NaN pattern.  Input layouts, mask / NaN conventions and the return
+    layout are janssen_inpaint's, and wherever that accepts the input the
+    result is the same bits: a cluster of one run goes to the same launch
+    (ops.janssen, the Toeplitz solver), all others to one launch of
+    ops.janssen_mask (banded Cholesky).  return_history: also a list with one
+    dict per cluster (signal, start, end: the hull of its missing samples,
+    missing: their indices in the signal, iters, history [maxit, h]: the
+    missing samples after every iteration, NaN for iterations not completed).
+    """
+    import torch
+    from . import ops
+    check_args(p, maxit)
+    method_id(method)
+    sigs, masks, kind = _normalise(signal, mask)
+    plan = plan_mask_segments(masks, w, p)
+    one = np.flatnonzero(plan.runs == 1)
+    many = np.flatnonzero(plan.runs > 1)
+    info = [None] * len(plan)
+    # every row is cut before anything is written back (no segment holds a
+    # missing sample of another cluster, so the order would not matter)
+    seg = Segments(plan.signal[one], plan.lo[one], plan.n[one],
+                   np.array([plan.missing[r][0] for r in one], np.int32),
+                   np.array([len(plan.missing[r]) for r in one], np.int32))
+    batch = None
+    if len(many):
+        batch = np.zeros((len(many), int(plan.n[many].max())), np.float64)
+        for k, r in enumerate(many):
+            lo, n = int(plan.lo[r]), int(plan.n[r])
+            batch[k, :n] = sigs[plan.signal[r]][lo:lo + n]
+    got, hist = _solve_segments(
+        sigs, seg, device, "iters",
+        lambda sol: ops.janssen(sol, seg.n, seg.gap_start, seg.gap_len, p, maxit,
+                                return_history=return_history, method=method))
+    for k, (r, d) in enumerate(zip(one, got)):
+        d["missing"] = np.arange(d["start"], d["end"])
+        d["history"] = hist[k, :, :int(seg.gap_len[k])].copy() if hist is not None else None
+        info[r] = d
+    if batch is not None:
+        sol = torch.from_numpy(batch).to(device)
+        lists = [plan.missing[r] for r in many]
+        count, hist = ops.janssen_mask(sol, plan.n[many], lists, p, maxit,
+                                       return_history=return_history, method=method)
+        sol, count = sol.cpu().numpy(), count.cpu().numpy()
+        hist = hist.cpu().numpy() if hist is not None else None
+        for k, r in enumerate(many):
+            idx = plan.missing[r].astype(np.int64)
+            where = int(plan.lo[r]) + idx
+            sigs[plan.signal[r]][where] = sol[k, idx]
+            info[r] = {"signal": int(plan.signal[r]), "start": int(where[0]),
+                       "end": int(where[-1]) + 1, "iters": int(count[k]), "missing": where,
+                       "history": hist[k, :, :len(idx)].copy() if hist is not None else None}
     out = restack(sigs, kind)
     return (out, info) if return_history else out
 

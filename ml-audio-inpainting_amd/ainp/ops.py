@@ -2173,6 +2173,48 @@ def janssen(sol, n, gap_start, gap_len, p, maxit, return_history=False, method="
     return iters, hist
 
 
+def janssen_mask(sol, n, missing, p, maxit, return_history=False, method="lpc"):
+    """ainp_janssen_mask: gap-wise Janssen AR inpainting for any set of missing
+    samples per segment (several gaps, scattered samples), float64, one
+    workgroup per segment for all maxit iterations; the missing samples come
+    from a banded Cholesky solve.  sol [n_segments, stride] float64 cuda,
+    updated in place (row i: n[i] samples, the samples missing[i] are zeroed
+    first).  missing: one integer array per row, strictly ascending indices
+    inside [0, n[i]), at most GAP_MAX of them; checked here.  An empty list
+    leaves its row alone (0 iterations).  method: "lpc" or "arburg".  Returns
+    (iters_done int32 [n_segments], history [n_segments, maxit, longest list]
+    float64 in list order, or None; NaN where nothing was recorded)."""
+    _jn.check_args(p, maxit)
+    m = _jn.method_id(method)
+    _req(sol, "sol", dtype=torch.float64)
+    if sol.dim() != 2:
+        raise ValueError("sol must be [n_segments, stride]")
+    nseg, stride = sol.shape
+    nn = np.asarray(n, dtype=np.int64).reshape(-1)
+    lists = [np.asarray(v, dtype=np.int64).reshape(-1) for v in missing]
+    if nn.size != nseg or len(lists) != nseg:
+        raise ValueError("n and missing need one entry per segment")
+    if nseg and not (np.all(nn > p) and np.all(nn <= min(stride, _jn.N_MAX))):
+        raise ValueError(f"every segment length must be in (p, min(stride, {_jn.N_MAX})]")
+    for i, v in enumerate(lists):
+        if v.size > _jn.GAP_MAX:
+            raise ValueError(f"row {i}: {v.size} missing samples, at most {_jn.GAP_MAX}")
+        if v.size and not (v[0] >= 0 and v[-1] < nn[i] and np.all(np.diff(v) > 0)):
+            raise ValueError(f"row {i}: the missing samples must ascend strictly inside "
+                             f"[0, {int(nn[i])})")
+    off = np.zeros(nseg + 1, np.int64)
+    np.cumsum([v.size for v in lists], out=off[1:])
+    h_max = max(1, int(max((v.size for v in lists), default=0)))
+    idx = np.concatenate(lists) if off[-1] else np.zeros(1, np.int64)
+    ws_bytes = _lib.lib.ainp_janssen_mask_workspace(nseg, min(stride, _jn.N_MAX), int(p), h_max, m)
+    iters, hist, ws = _row_outputs(sol.device, nseg,
+                                   (nseg, int(maxit), h_max) if return_history else None, ws_bytes)
+    if nseg:
+        _T.janssen_mask(sol, _dev_i32(nn, sol.device), _dev_i32(off, sol.device),
+                        _dev_i32(idx, sol.device), h_max, int(p), int(maxit), m, hist, iters, ws)
+    return iters, hist
+
+
 def ar_extrapolate(sol, n, gap_start, gap_len, p, w, method="lpc"):
     """ainp_ar_extrapolate: forward/backward AR extrapolation of one gap per
     segment (the reference's arinpaint.m), float64.  sol [n_segments, stride]

@@ -1,4 +1,4 @@
-// ar_limits.h — the size limits of the audio-regression kernels (janssen.hip,
+// ar_limits.h — the size limits of the audio-regression kernels (janssen.hip, janssen_mask.hip,
 // ar_extrapolate.hip, janssen_windows.hip, and through spain_window.h and
 // spain_plan.h spain.hip and spain_omp.hip), host and device.  The Python host
 // layer restates them (ainp/janssen.py: P_MAX, N_MAX, GAP_MAX, MAXIT_MAX).

@@ -259,6 +259,50 @@ void janssen(const Tensor& sol, const Tensor& n, const Tensor& gap_start, const 
       "janssen");
 }
 
+// any set of missing samples per row: miss_off [n_segments + 1] and miss_idx are
+// on the device; the offsets are read back and checked against miss_idx here,
+// the lists themselves by the kernel's guard
+void janssen_mask(const Tensor& sol, const Tensor& n, const Tensor& miss_off,
+                  const Tensor& miss_idx, int64_t h_max, int64_t p, int64_t maxit, int64_t method,
+                  const OptT& history, const Tensor& iters_done, const OptT& workspace) {
+  GUARD(sol);
+  TORCH_CHECK(sol.dim() == 2, "sol must be [n_segments, stride]");
+  TORCH_CHECK(method == AINP_AR_LPC || method == AINP_AR_BURG,
+              "method must be 0 (lpc) or 1 (arburg)");
+  const int64_t n_seg = sol.size(0);
+  double* x = dev<double>(sol, "sol", at::kDouble);
+  const auto tab = row_tables(sol, n_seg, {{n, "n"}, {iters_done, "iters_done"}});
+  numel_is(miss_off, n_seg + 1, "miss_off");
+  same_device(sol, miss_off);
+  same_device(sol, miss_idx);
+  const int32_t* off = dev<int32_t>(miss_off, "miss_off", at::kInt);
+  const int32_t* idx = dev<int32_t>(miss_idx, "miss_idx", at::kInt);
+  TORCH_CHECK(p >= 1 && p <= INT32_MAX && maxit >= 1 && maxit <= INT32_MAX && h_max >= 1 &&
+                  h_max <= INT32_MAX,
+              "p, maxit and h_max must be positive");
+  {
+    const Tensor host = miss_off.cpu();
+    const int32_t* o = host.data_ptr<int32_t>();
+    bool ok = o[0] >= 0 && o[n_seg] <= miss_idx.numel();
+    for (int64_t i = 0; i < n_seg && ok; ++i) ok = o[i + 1] >= o[i] && o[i + 1] - o[i] <= h_max;
+    TORCH_CHECK(ok, "miss_off must ascend from >= 0 to <= miss_idx.numel() in steps of at most "
+                    "h_max");
+  }
+  double* h = opt<double>(history, "history", at::kDouble);
+  int64_t hist_row = 0;
+  if (h) {
+    same_device(sol, *history);
+    TORCH_CHECK(history->dim() == 3 && history->size(0) == n_seg && history->size(1) == maxit &&
+                    history->size(2) >= h_max,
+                "history must be [n_segments, maxit, >= h_max], got ", history->sizes());
+    hist_row = history->size(2);
+  }
+  const auto [ws, ws_bytes] = byte_workspace(sol, workspace);
+  chk(ainp_janssen_mask(x, n_seg, sol.size(1), tab[0], off, idx, (int)h_max, (int)p, (int)maxit,
+                        (int)method, h, hist_row, tab[1], ws, ws_bytes, stream_of(sol)),
+      "janssen_mask");
+}
+
 void ar_extrapolate(const Tensor& sol, const Tensor& n, const Tensor& gap_start,
                     const Tensor& gap_len, int64_t p, int64_t w, int64_t method,
                     const Tensor& status, const OptT& workspace) {
@@ -2129,6 +2173,9 @@ TORCH_LIBRARY(ainp, m) {
   m.def("mel_inverse(Tensor pinv, Tensor mel, int flags, Tensor(a!) out) -> ()");
   m.def("janssen(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int maxit, "
         "Tensor(b!)? history, Tensor(c!) iters_done, Tensor? workspace, int method=0) -> ()");
+  m.def("janssen_mask(Tensor(a!) sol, Tensor n, Tensor miss_off, Tensor miss_idx, int h_max, int p, "
+        "int maxit, int method, Tensor(b!)? history, Tensor(c!) iters_done, Tensor? workspace) "
+        "-> ()");
   m.def("ar_extrapolate(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int w, "
         "int method, Tensor(b!) status, Tensor? workspace) -> ()");
   m.def("janssen_windows(Tensor signals, Tensor sig_off, Tensor row_tab, Tensor gap_start, "
@@ -2236,6 +2283,7 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("mel_fwd", &mel_fwd);
   m.impl("mel_inverse", &mel_inverse);
   m.impl("janssen", &janssen);
+  m.impl("janssen_mask", &janssen_mask);
   m.impl("ar_extrapolate", &ar_extrapolate);
   m.impl("janssen_windows", &janssen_windows);
   m.impl("janssen_ola", &janssen_ola);
@@ -2334,6 +2382,7 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("mel_fwd", torch::CppFunction::makeFallthrough());
   m.impl("mel_inverse", torch::CppFunction::makeFallthrough());
   m.impl("janssen", torch::CppFunction::makeFallthrough());
+  m.impl("janssen_mask", torch::CppFunction::makeFallthrough());
   m.impl("ar_extrapolate", torch::CppFunction::makeFallthrough());
   m.impl("janssen_windows", torch::CppFunction::makeFallthrough());
   m.impl("janssen_ola", torch::CppFunction::makeFallthrough());

@@ -21,6 +21,8 @@ Follows models/model_eval.py:23-227 step by step, on the MI355X kernels:
                             baseline (models/AudioReg; the third row of
                             models/AudioReg/model_eval.m's SDR table) ->
                             <name>_janssen_inpainted.flac and the gap SDRs
+  run_janssen_mask_evaluation  the same with several gaps per clip, gaps closer
+                            than w filled together (janssen_inpaint_mask)
   run_ar_evaluation         any cell of models/AudioReg/train.m's table: Janssen
                             or forward/backward extrapolation, "lpc" or "arburg"
   run_spain_evaluation      the sparsity row they are compared against
@@ -160,10 +162,13 @@ def run_evaluation(input_dir, output_dir, model_type, checkpoint, config_path):
     return outs
 
 
-def _evaluate_gap_filler(input_dir, output_dir, suffix, fill):
-    """What the signal-processing rows share: the clips with their gap go to
+def _evaluate_gap_filler(input_dir, output_dir, suffix, fill,
+                         gaps=((GAP_START_S, GAP_LEN_S),)):
+    """What the signal-processing rows share: the clips with their gaps
+    ((start_s, length_s) each; inpaint()'s one by default) go to
     fill(clean, masks) -> restored as one batch, the results to
-    <stem>_<suffix>_inpainted.flac, the gap SDRs to the caller."""
+    <stem>_<suffix>_inpainted.flac, the SDRs over all missing samples to the
+    caller."""
     from models.AudioReg import gap_sdr
     if not os.path.isdir(input_dir):
         print(f"Error: Input directory not found: {input_dir}")
@@ -176,9 +181,12 @@ def _evaluate_gap_filler(input_dir, output_dir, suffix, fill):
     clean, masks, srs = [], [], []
     for filename in flac_files:
         audio, sr = utils.load_audio(os.path.join(input_dir, filename))
-        mask_td, _ = utils.create_gap_mask(len(audio), GAP_LEN_S, sr, gap_start_s=GAP_START_S)
+        observed = np.ones(len(audio), bool)
+        for start_s, length_s in gaps:
+            mask_td, _ = utils.create_gap_mask(len(audio), length_s, sr, gap_start_s=start_s)
+            observed &= mask_td > 0
         clean.append(audio.astype(np.float64))
-        masks.append(mask_td > 0)
+        masks.append(observed)
         srs.append(sr)
     restored = fill(clean, masks) if clean else []
     sdrs = {}
@@ -195,6 +203,22 @@ def run_janssen_evaluation(input_dir, output_dir, p=512, w=4096, maxit=20):
     Returns {filename: gap SDR in dB} (models/AudioReg/model_eval.m:60)."""
     return run_ar_evaluation(input_dir, output_dir, algorithm="janssen", method="lpc", p=p, w=w,
                              maxit=maxit)
+
+
+def run_janssen_mask_evaluation(input_dir, output_dir, gaps=((2.0, 0.08),), p=512, w=4096,
+                                maxit=20, method="lpc"):
+    """run_janssen_evaluation for a list of (start_s, length_s) gaps per clip:
+    janssen_inpaint_mask fills them, gaps closer than w samples to one another
+    together.  Each result is written as <stem>_janssen_mask[_arburg]_inpainted.flac.
+    Returns {filename: SDR over all missing samples in dB}; with the default
+    gap these are run_janssen_evaluation's figures."""
+    from models.AudioReg import janssen_inpaint_mask
+    from ainp.janssen import method_id
+    return _evaluate_gap_filler(
+        input_dir, output_dir, "janssen_mask" + ("_arburg" if method_id(method) else ""),
+        lambda clean, masks: janssen_inpaint_mask(clean, masks, p=p, w=w, maxit=maxit,
+                                                  method=method),
+        gaps=tuple((float(s), float(g)) for s, g in gaps))
 
 
 AR_ALGORITHMS = ("extrapolation", "janssen", "janssen_hann", "janssen_rect", "janssen_tukey")
