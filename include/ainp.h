@@ -159,6 +159,54 @@ int ainp_mel_fwd(const void* spec, int dtype, int64_t n_signals, int n_bins,
 int ainp_mel_inverse(const float* pinv, const float* mel, int64_t n_signals, int n_bins,
                      int n_mels, int64_t n_frames, int flags, float* out, void* stream);
 
+/* Rational-ratio polyphase FIR resampling, scipy.signal.resample_poly(x, up,
+ * down) with its defaults (window=("kaiser", 5.0), padtype="constant"; the
+ * 48 kHz export of models/AudioReg/train.m:72,203 and utils.load_audio's
+ * resampling), csrc/resample.hip.  With g = gcd(up, down), up /= g, down /= g,
+ * R = max(up, down), half = 10 R, L = 2 half + 1 and
+ *   h[t] = up sinc((t - half) / R) / R kaiser_5(L)[t] / sum(the same without up),
+ * row r of y is
+ *   y[r][m] = sum_i x[r][i] h[m down + half - i up],  0 <= i < n_in[r],
+ * the h index in [0, L), for m < min(ceil(n_in[r] up / down), stride_out), and
+ * zero for the rest of the row up to stride_out: truncation or zero padding to
+ * a common length happens in the same pass.  up == down after reduction is a
+ * copy with the same zero fill.  The products are summed by fma in the element
+ * type (dtype 0: float32, 1: float64), as scipy filters float32 input with a
+ * float32 filter.
+ * x [rows][stride_in], y [rows][stride_out], n_in int32 [rows] on the device
+ * (values outside [0, stride_in] are clamped); samples of a row beyond
+ * n_in[r] are never read.  table: the filter in the element type, phase-major
+ * [up][pitch] as ainp_resample_plan_query lays it out (ainp/resample.py builds
+ * it on the host in float64): table[p][k] = h[p + (tpp - 1 - k) up], zero where
+ * that index is >= L or k >= tpp; NULL for a copy.
+ * rows == 0 or stride_out == 0 is a no-op.  up, down >= 1, n_in <= 2^31 - 1,
+ * rows <= 65535 (the grid's second axis), table 16-byte aligned; a
+ * ratio whose filter cannot be staged (see csrc/resample_plan.h) and any other
+ * bad argument is AINP_EINVAL without a launch. */
+#define AINP_RS_COPY 0          /* up == down after reduction */
+#define AINP_RS_LDS_TABLE 1     /* the table and a tile's input span in LDS */
+#define AINP_RS_GLOBAL_TABLE 2  /* the span in LDS, coefficients read through L2 */
+typedef struct AinpResamplePlan {
+  int up, down;   /* reduced by their gcd */
+  int half, taps; /* 10 max(up, down) and L = 2 half + 1 (0 for a copy) */
+  int tpp;        /* taps per phase, ceil(L / up) */
+  int pitch;      /* elements between two phases of the table (>= tpp, odd) */
+  int tile;       /* outputs per workgroup */
+  int span;       /* inputs a tile reads, the first being
+                     floor((m0 down + half) / up) - tpp + 1 for its first output m0 */
+  int route;      /* AINP_RS_* */
+  int64_t table_elems; /* up * pitch */
+  int64_t lds_bytes;   /* LDS of one workgroup */
+} AinpResamplePlan;
+int ainp_resample_poly(void* y, const void* x, const void* table, int64_t rows,
+                       int64_t stride_in, int64_t stride_out, const int32_t* n_in, int up,
+                       int down, int dtype, void* stream);
+/* ceil(n_in up / down) in exact integer arithmetic; -1 for a bad argument */
+int64_t ainp_resample_out_len(int64_t n_in, int up, int down);
+/* Host-only: the plan ainp_resample_poly launches with.  AINP_EINVAL (and
+ * *plan zeroed) for a ratio it refuses. */
+int ainp_resample_plan_query(int up, int down, int dtype, AinpResamplePlan* plan);
+
 /* Gap-wise Janssen autoregressive inpainting, the AR row of the reference's
  * model comparison (models/AudioReg/utils/janssen_inp.m, method "lpc", as
  * models/AudioReg/train.m drives it).  Float64 throughout.  sol

@@ -48,6 +48,12 @@ class ConvGenPlan(ctypes.Structure):
         ("refusal", c_char_p)]
 
 
+class ResamplePlan(ctypes.Structure):
+    """AinpResamplePlan (include/ainp.h)."""
+    _fields_ = [(n, c_int) for n in ("up", "down", "half", "taps", "tpp", "pitch", "tile", "span",
+                                     "route")] + [("table_elems", c_int64), ("lds_bytes", c_int64)]
+
+
 _SIGS = {
     "ainp_abi_version": (c_int, []),
     "ainp_build_target": (c_char_p, []),
@@ -250,6 +256,11 @@ _SIGS = {
     "ainp_mel_fwd": (c_int, [P, c_int, c_int64, c_int, c_int64, P, P, P, c_int64, c_int,
                              c_double, P, P]),
     "ainp_mel_inverse": (c_int, [P, P, c_int64, c_int, c_int, c_int64, c_int, P, P]),
+    # polyphase resampling and its host queries (csrc/resample.hip, resample_plan.h)
+    "ainp_resample_poly": (c_int, [P, P, P, c_int64, c_int64, c_int64, P, c_int, c_int, c_int,
+                                   P]),
+    "ainp_resample_out_len": (c_int64, [c_int64, c_int, c_int]),
+    "ainp_resample_plan_query": (c_int, [c_int, c_int, c_int, POINTER(ResamplePlan)]),
     # Janssen autoregressive gap inpainting (csrc/janssen.hip)
     "ainp_janssen": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "ainp_janssen_workspace": (c_size_t, [c_int64, c_int, c_int, c_int]),

@@ -27,6 +27,7 @@ import torch
 from . import _lib
 from . import janssen as _jn
 from . import mel as _mel
+from . import resample as _rs
 from . import spain as _sp
 
 # AINP_TORCH_OPS: another build of the same registration (e.g. the UBSan build
@@ -52,7 +53,7 @@ def _release_device_caches():
     except Exception:   # noqa: BLE001 -- best effort at interpreter exit
         pass
     for c in (_WIN_CACHE, _GEMM_WS, _EMPTY, _WT_CACHE, _WT16_CACHE, _RED_WS,
-              _mel._DEVICE_CACHE):
+              _mel._DEVICE_CACHE, _rs._DEVICE_CACHE):
         c.clear()
 
 
@@ -2106,6 +2107,48 @@ def mel_to_linear(M, sr=22050, n_fft=2048, n_mels=128, fmin=0.0, fmax=None, powe
         flags = MEL_SQRT | (MEL_CLAMP if clamp_negative else 0)
     out = mel_inverse(P, M.reshape(-1, K, T).contiguous(), flags)
     return out.reshape(*lead, P.shape[0], T)
+
+
+# =============================================================== resample
+def resample_poly(x, up, down, n=None, out_len=None):
+    """scipy.signal.resample_poly(x, up, down) with its defaults, row by row on
+    the GPU (ainp_resample_poly): x [n] or [rows, stride] float32 / float64 cuda
+    -> [out_len] or [rows, out_len] of the same dtype.  n: the rows' lengths
+    (int32 cuda tensor or a list; default: the full stride) -- samples beyond
+    them are never read.  out_len truncates or zero-pads every row to that
+    length in the same pass; default: the longest row's ceil(n * up / down)."""
+    _req(x, "x", dtype=None)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError("x must be float32 or float64")
+    if x.dim() not in (1, 2):
+        raise ValueError("x must be [n] or [rows, stride]")
+    p = _rs.plan(up, down, x.dtype)     # AinpError (EINVAL) for a ratio it refuses
+    x2 = x.reshape(1, -1) if x.dim() == 1 else x
+    rows, stride = x2.shape
+    if n is None:
+        n_max = stride
+        n_dev = torch.full((rows,), stride, dtype=torch.int32, device=x.device)
+    else:
+        if isinstance(n, torch.Tensor):
+            n_dev = _req(n, "n", dtype=torch.int32).reshape(-1)
+            n_host = n_dev.tolist() if out_len is None else None
+        else:
+            n_host = [int(v) for v in np.asarray(n).reshape(-1)]
+            n_dev = _dev_i32(n_host, x.device)
+        if n_dev.numel() != rows:
+            raise ValueError(f"n has {n_dev.numel()} entries, x has {rows} rows")
+        if n_host is not None and any(v < 0 or v > stride for v in n_host):
+            raise ValueError("every n must lie in [0, stride]")
+        n_max = max(n_host, default=0) if n_host is not None else stride
+    if out_len is None:
+        out_len = _rs.out_len(n_max, up, down)
+    out_len = int(out_len)
+    if out_len < 0:
+        raise ValueError("out_len must be >= 0")
+    table = None if p.route == _rs.RS_COPY else _rs.device_table(up, down, x.dtype, x.device)
+    out = torch.empty(rows, out_len, device=x.device, dtype=x.dtype)
+    _T.resample_poly(x2, table, n_dev, int(up), int(down), out)
+    return out.reshape(-1) if x.dim() == 1 else out
 
 
 # ================================================================ Janssen

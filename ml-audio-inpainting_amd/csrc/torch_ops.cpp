@@ -13,11 +13,15 @@
 // tensor fails in the dispatcher -- there is no CPU path.
 //
 // Host-only queries (workspace sizes, stat-part counts) and the FLAC codec
-// stay on the plain C ABI (ctypes); they launch nothing.
+// stay on the plain C ABI (ctypes); they launch nothing.  The resampler's two
+// (resample_out_len, resample_plan_query) are operators without tensor
+// arguments as well.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/library.h>
+
+#include <limits.h>
 
 #include <algorithm>
 #include <initializer_list>
@@ -210,6 +214,56 @@ void mel_inverse(const Tensor& pinv, const Tensor& mel, int64_t flags, const Ten
                        (int)pinv.size(1), mel.size(2), (int)flags, dev(out, "out"),
                        stream_of(mel)),
       "mel_inverse");
+}
+
+// --------------------------------------------------------------- resample
+void resample_poly(const Tensor& x, const OptT& table, const Tensor& n_in, int64_t up,
+                   int64_t down, const Tensor& out) {
+  GUARD(x);
+  TORCH_CHECK(x.dim() == 2, "x must be [rows, stride_in]");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == x.size(0), "out is ", out.sizes(),
+              ", expected [", x.size(0), ", out_len]");
+  const bool f64 = x.scalar_type() == at::kDouble;
+  const at::ScalarType st = f64 ? at::kDouble : at::kFloat;
+  const void* xp = dev<void>(x, "x", st);
+  void* yp = dev<void>(out, "out", st);
+  same_device(x, out);
+  same_device(x, n_in);
+  numel_is(n_in, x.size(0), "n_in");
+  TORCH_CHECK(up >= INT_MIN && up <= INT_MAX && down >= INT_MIN && down <= INT_MAX,
+              "up and down must fit an int");
+  AinpResamplePlan plan;
+  chk(ainp_resample_plan_query((int)up, (int)down, f64 ? 1 : 0, &plan), "resample_plan_query");
+  const void* tp = nullptr;
+  if (plan.route != AINP_RS_COPY) {
+    TORCH_CHECK(table.has_value() && table->defined(), "table is required unless up == down");
+    tp = dev<void>(*table, "table", st);
+    same_device(x, *table);
+    numel_is(*table, plan.table_elems, "table");
+  }
+  chk(ainp_resample_poly(yp, xp, tp, x.size(0), x.size(1), out.size(1),
+                         dev<int32_t>(n_in, "n_in", at::kInt), (int)up, (int)down, f64 ? 1 : 0,
+                         stream_of(x)),
+      "resample_poly");
+}
+
+// host-only: the C queries as operators without tensor arguments
+int64_t resample_out_len(int64_t n_in, int64_t up, int64_t down) {
+  TORCH_CHECK(up >= INT_MIN && up <= INT_MAX && down >= INT_MIN && down <= INT_MAX,
+              "up and down must fit an int");
+  const int64_t n = ainp_resample_out_len(n_in, (int)up, (int)down);
+  TORCH_CHECK(n >= 0, "resample_out_len: 0 <= n_in <= 2^31 - 1, up >= 1, down >= 1");
+  return n;
+}
+
+// (up, down, half, taps, tpp, pitch, tile, span, route, table_elems, lds_bytes)
+std::vector<int64_t> resample_plan_query(int64_t up, int64_t down, int64_t dtype) {
+  TORCH_CHECK(up >= INT_MIN && up <= INT_MAX && down >= INT_MIN && down <= INT_MAX,
+              "up and down must fit an int");
+  AinpResamplePlan p;
+  chk(ainp_resample_plan_query((int)up, (int)down, (int)dtype, &p), "resample_plan_query");
+  return {p.up, p.down, p.half, p.taps, p.tpp, p.pitch, p.tile, p.span, p.route,
+          p.table_elems, p.lds_bytes};
 }
 
 // ---------------------------------------------------------------- Janssen
@@ -2171,6 +2225,10 @@ TORCH_LIBRARY(ainp, m) {
   m.def("mel_fwd(Tensor spec, Tensor band_lo, Tensor band_off, Tensor weights, float power, "
         "Tensor(a!) out) -> ()");
   m.def("mel_inverse(Tensor pinv, Tensor mel, int flags, Tensor(a!) out) -> ()");
+  m.def("resample_poly(Tensor x, Tensor? table, Tensor n_in, int up, int down, Tensor(a!) out) "
+        "-> ()");
+  m.def("resample_out_len(int n_in, int up, int down) -> int", &resample_out_len);
+  m.def("resample_plan_query(int up, int down, int dtype) -> int[]", &resample_plan_query);
   m.def("janssen(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int maxit, "
         "Tensor(b!)? history, Tensor(c!) iters_done, Tensor? workspace, int method=0) -> ()");
   m.def("janssen_mask(Tensor(a!) sol, Tensor n, Tensor miss_off, Tensor miss_idx, int h_max, int p, "
@@ -2282,6 +2340,7 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("conv_weight_flip_t", &conv_weight_flip_t);
   m.impl("mel_fwd", &mel_fwd);
   m.impl("mel_inverse", &mel_inverse);
+  m.impl("resample_poly", &resample_poly);
   m.impl("janssen", &janssen);
   m.impl("janssen_mask", &janssen_mask);
   m.impl("ar_extrapolate", &ar_extrapolate);
@@ -2381,6 +2440,7 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("conv_weight_flip_t", torch::CppFunction::makeFallthrough());
   m.impl("mel_fwd", torch::CppFunction::makeFallthrough());
   m.impl("mel_inverse", torch::CppFunction::makeFallthrough());
+  m.impl("resample_poly", torch::CppFunction::makeFallthrough());
   m.impl("janssen", torch::CppFunction::makeFallthrough());
   m.impl("janssen_mask", torch::CppFunction::makeFallthrough());
   m.impl("ar_extrapolate", torch::CppFunction::makeFallthrough());

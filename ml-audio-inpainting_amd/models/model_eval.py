@@ -27,18 +27,22 @@ Follows models/model_eval.py:23-227 step by step, on the MI355X kernels:
                             or forward/backward extrapolation, "lpc" or "arburg"
   run_spain_evaluation      the sparsity row they are compared against
                             (models/AudioReg/references/spain): A-SPAIN or S-SPAIN
+  export_48k_pairs          the clean / restored pairs at 48 kHz that the
+                            perceptual metrics of models/AudioReg/train.m take
+                            (GPU polyphase resampler, ainp_resample_poly)
 Spectrogram plots (:157-162,180-185) are out of scope (plotting).  The ISTFT
 runs on the GPU (ainp_istft); output length hop * (T - 1), as librosa's.
 """
 from __future__ import annotations
 
+import math
 import os
 import sys
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+HERE =os.path.dirname(os.path.abspath(__file__))
 _PKG = os.path.dirname(HERE)
 for _p in (HERE, _PKG):
     if _p not in sys.path:
@@ -293,6 +297,57 @@ def run_spain_learned_evaluation(input_dir, output_dir, basis=None, algorithm="a
         input_dir, output_dir, f"{algorithm}_{'global' if basis is None else 'learned'}",
         lambda clean, masks: spain_learned_inpaint(clean, masks, basis=basis, algorithm=algorithm,
                                                    w=w, a=a, **solver))
+
+
+EXPORT_SR = 48000     # models/AudioReg/train.m:72, model_eval.m:68: what PEMO-Q and PEAQ take
+
+
+def export_48k_pairs(input_dir, reconstructed_dir, output_dir, suffix):
+    """models/AudioReg/train.m:72-73,203-204 (model_eval.m:68-71): the clean and
+    the restored signal resampled to 48 kHz for the perceptual metrics.  For
+    every <stem>.flac of input_dir with a <stem>_<suffix>_inpainted.flac in
+    reconstructed_dir, writes <stem>_signal.wav and <stem>_<suffix>_solution.wav
+    to output_dir: 48 kHz, resampled in float64 on the GPU, all clips of one
+    native rate in one launch, saved without normalisation as audiowrite saves
+    them.  Returns the list of (signal path, solution path).  PEMO-Q and PEAQ
+    themselves are closed toolboxes and stay out of scope."""
+    from ainp import ops
+    if not os.path.isdir(input_dir):
+        print(f"Error: Input directory not found: {input_dir}")
+        return []
+    if not torch.cuda.is_available():
+        raise RuntimeError("model_eval runs on the MI355X kernels: no GPU visible")
+    os.makedirs(output_dir, exist_ok=True)
+    jobs, by_rate = [], {}     # (clip, output path); rows of jobs per native rate
+    pairs = []
+    for filename in sorted(f for f in os.listdir(input_dir) if f.lower().endswith(".flac")):
+        stem = os.path.splitext(filename)[0]
+        restored = os.path.join(reconstructed_dir, f"{stem}_{suffix}_inpainted.flac")
+        if not os.path.exists(restored):
+            continue
+        outs = (os.path.join(output_dir, f"{stem}_signal.wav"),
+                os.path.join(output_dir, f"{stem}_{suffix}_solution.wav"))
+        for path, out in zip((os.path.join(input_dir, filename), restored), outs):
+            try:
+                data, sr = utils._read_any(path)
+            except Exception as e:
+                raise IOError(f"Error loading audio file {path}: {str(e)}")
+            by_rate.setdefault(int(sr), []).append(len(jobs))
+            jobs.append((data.mean(axis=1).astype(np.float64), out))
+        pairs.append(outs)
+    for sr, rows in by_rate.items():
+        g = math.gcd(sr, EXPORT_SR)
+        n = [len(jobs[k][0]) for k in rows]
+        stride = max(2, -(-max(n) // 2) * 2)     # rows stay 16-byte aligned
+        host = np.zeros((len(rows), stride), dtype=np.float64)
+        for j, k in enumerate(rows):
+            host[j, :n[j]] = jobs[k][0]
+        y = ops.resample_poly(torch.from_numpy(host).cuda(), EXPORT_SR // g, sr // g, n=n).cpu()
+        for j, k in enumerate(rows):
+            n_out = -(-n[j] * (EXPORT_SR // g) // (sr // g))
+            utils.save_audio(y[j, :n_out].numpy(), file_path=jobs[k][1], sample_rate=EXPORT_SR,
+                             normalize=False, file_format="wav")
+    return pairs
 
 
 if __name__ == "__main__":

@@ -18,6 +18,11 @@ Same names, signatures, return types and error behaviour as
   mel_spectrogram_to_audio  utils.py:335-393 (GPU: ainp_mel_inverse + Griffin-Lim;
                                           clamp_negative deviates from the
                                           reference's NaN, see its docstring)
+  resample_audio, load_audio_batch   (not in the reference's utils.py) the
+                                          polyphase resampler ainp_resample_poly:
+                                          models/AudioReg/train.m:72's 48 kHz
+                                          resample(), and load_audio for a batch
+                                          with the resampling on the GPU
 Plotting (visualize_spectrogram) is outside the hot path.
 """
 from __future__ import annotations
@@ -109,6 +114,68 @@ def load_audio(file_path: Union[str, Path], sample_rate: int = DEFAULT_SAMPLE_RA
         return audio_data, sr
     except Exception as e:
         raise IOError(f"Error loading audio file {file_path}: {str(e)}")
+
+
+def resample_audio(audio, orig_sr: int, target_sr: int):
+    """scipy.signal.resample_poly(audio, target_sr / g, orig_sr / g) with
+    g = gcd(orig_sr, target_sr), along the last axis, on the GPU
+    (ainp_resample_poly; MATLAB resample(x, p, q) of models/AudioReg/train.m:72).
+    audio [n] or [rows, n], float32 or float64 (anything else is computed in
+    float64): a numpy array comes back as a numpy array, a cuda tensor stays on
+    the device; the dtype is kept."""
+    import torch
+    from math import gcd
+    from ainp import ops
+    orig_sr, target_sr = int(orig_sr), int(target_sr)
+    if orig_sr < 1 or target_sr < 1:
+        raise ValueError("sample rates must be positive")
+    g = gcd(orig_sr, target_sr)
+    if isinstance(audio, torch.Tensor):
+        return ops.resample_poly(audio.contiguous(), target_sr // g, orig_sr // g)
+    x = np.asarray(audio)
+    if x.dtype not in (np.float32, np.float64):
+        x = x.astype(np.float64)
+    y = ops.resample_poly(torch.from_numpy(np.ascontiguousarray(x)).cuda(), target_sr // g,
+                          orig_sr // g)
+    return y.cpu().numpy()
+
+
+def load_audio_batch(file_paths, sample_rate: int = DEFAULT_SAMPLE_RATE, max_len=5,
+                     mono: bool = True):
+    """load_audio for a list of files, resampled on the GPU: every file is
+    decoded on the host as load_audio decodes it (mono mean first), the files
+    are grouped by native rate, and each group is one ainp_resample_poly launch
+    that also truncates or zero-pads to int(sample_rate * max_len) samples.
+    Returns a cuda float32 tensor [len(file_paths), int(sample_rate * max_len)]
+    in input order; a file that fails to decode raises IOError naming it."""
+    import torch
+    from math import gcd
+    from ainp import ops
+    if not mono:
+        raise ValueError("load_audio_batch returns one row per file: mono only")
+    sample_rate = int(sample_rate)
+    max_samples = int(sample_rate * max_len)
+    clips, by_rate = [], {}
+    for k, path in enumerate(file_paths):
+        try:
+            data, sr = _read_any(path)
+            clips.append(np.ascontiguousarray(data.mean(axis=1), dtype=np.float32))
+            by_rate.setdefault(int(sr), []).append(k)
+        except Exception as e:
+            raise IOError(f"Error loading audio file {path}: {str(e)}")
+    out = torch.empty(len(clips), max_samples, device="cuda", dtype=torch.float32)
+    for sr, rows in by_rate.items():
+        g = gcd(sr, sample_rate)
+        n = [len(clips[k]) for k in rows]
+        # a multiple of four samples keeps every row 16-byte aligned
+        stride = max(4, -(-max(n) // 4) * 4)
+        host = np.zeros((len(rows), stride), dtype=np.float32)
+        for j, k in enumerate(rows):
+            host[j, :n[j]] = clips[k]
+        y = ops.resample_poly(torch.from_numpy(host).cuda(), sample_rate // g, sr // g, n=n,
+                              out_len=max_samples)
+        out[torch.as_tensor(rows, device="cuda")] = y
+    return out
 
 
 def save_audio(audio_data: np.ndarray, file_path: Union[str, Path],
