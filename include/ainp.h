@@ -387,6 +387,65 @@ int ainp_janssen_ola(const double* sol, int64_t n_rows, int64_t stride,
                      double* signals, int64_t total, double* history, int64_t out_stride,
                      void* stream);
 
+/* The same two streams for any mask (utils/segmentation_inp.m called on a whole
+ * signal with any NaN pattern; ainp.janssen.janssen_windowed_mask).  The support
+ * is the signal from its first sample, zero-padded (observed zeros) to the
+ * circular length L = ceil(sig_len / a) * a + (w / a - 1) * a; the S = L / a
+ * windows are those above and do not depend on the mask.  A row is a window
+ * with some, not all, samples missing, in any number of runs: rows of one run
+ * in window order are solved by ainp_janssen_ex, the others by
+ * ainp_janssen_mask, both with n = w.
+ *
+ * ainp_janssen_windows_mask cuts the rows: sol[r][i] = signal sample *
+ * gana[shape][i], zero where missing[] is non-zero and on the padding.
+ * signals, sig_off, gana, sol, stride as above; missing: `total` bytes laid
+ * out like signals, non-zero on a missing sample.  row_tab int32 [n_rows][4]:
+ * sig_len, L, window index, shape.  A row whose entries contradict one another
+ * (L < w, sig_len > L, window index * a >= L, shape >= n_shapes, a signal
+ * outside [0, total)) is written as zeros.
+ *
+ * ainp_janssen_ola_mask puts the runs of missing samples back, one lane per
+ * missing sample.  run_off int64 [n_runs]: the run's first sample in
+ * `signals`; run_tab int32 [n_runs][5]: h (its samples; not limited to 2048),
+ * c0 (signal index of the first), L, tab0, shape.  win_row int32 [n_tab]:
+ * win_row[tab0 + s] is the row of window s of the run's (shape, signal), -1
+ * for a window without a row -- with the wrap of the last windows to the head
+ * of the signal a run's rows are not consecutive.  Per missing sample c = c0 + j
+ *   value = sum_s sol[win_row[tab0 + s]][i_s] * gsyn[shape][i_s] / rescale,
+ *   rescale = sum_s gana[shape][i_s] * gsyn[shape][i_s],
+ *   i_s = (c - s * a + floor(w / 2)) mod L,
+ * over the w / a windows s with i_s < w in ascending s; windows without a row
+ * add zero to the first sum.  A table entry that does not name a row of window
+ * s, shape and L is taken as no row.  The value goes to signals[run_off + j];
+ * observed samples are never written.
+ * history (nullable) [n_runs][maxit][out_stride] from row_history
+ * [n_rows][maxit][hist_stride] (both or neither), where a row's history is in
+ * the order of its missing list: position i_s - gap_start[r] for a row of one
+ * run (gap_len[r] >= 1), else (gap_len[r] == 0) the index of i_s in the row's
+ * strictly ascending list miss_idx[miss_off[r] .. miss_off[r + 1]) (miss_off
+ * int32 [n_rows + 1], miss_idx int32 [n_idx], n_idx >= 1), found by a
+ * lower-bound search; a sample that is not in its row's list adds nothing.  A
+ * NaN of row_history goes through the sum.  No atomics, fixed order: the same
+ * bits on every call.  A run whose entries contradict one another or reach
+ * outside `signals` or win_row is skipped.
+ * Supported: as above for w, a, stride, n_shapes, total; ola also 1 <= h_max
+ * <= total (the longest h, sizes the grid: at most 65535 * 256) and with
+ * history 1 <= maxit <= 1000, hist_stride >= 1, out_stride >= h_max.  Anything
+ * else is AINP_EINVAL without a launch.  Neither needs a workspace. */
+int ainp_janssen_windows_mask(const double* signals, const uint8_t* missing, int64_t total,
+                              const int64_t* sig_off, const int32_t* row_tab, int64_t n_rows,
+                              int w, int a, const double* gana, int n_shapes, double* sol,
+                              int64_t stride, void* stream);
+int ainp_janssen_ola_mask(const double* sol, int64_t n_rows, int64_t stride,
+                          const double* row_history, int maxit, int64_t hist_stride,
+                          const int32_t* row_tab, const int32_t* gap_start,
+                          const int32_t* gap_len, const int32_t* miss_off,
+                          const int32_t* miss_idx, int64_t n_idx, const int32_t* win_row,
+                          int64_t n_tab, const int64_t* run_off, const int32_t* run_tab,
+                          int64_t n_runs, int64_t h_max, int w, int a, const double* gana,
+                          const double* gsyn, int n_shapes, double* signals, int64_t total,
+                          double* history, int64_t out_stride, void* stream);
+
 /* The two SPAIN algorithms (references/spain/aspain.m and sspain.m with
  * f_update = 'H'): the analysis and the synthesis variant of sparse audio
  * inpainting by ADMM with a hard threshold. */

@@ -2,7 +2,9 @@
 ainp/spain.py): the input layouts and the gap SDR, the windows of
 utils/segmentation_inp.m, and the window-wise batch -- the rows a gap makes on
 a circular support (window_rows), the tables of csrc/janssen_windows.hip
-(window_plan) and the three launches around a solver (solve_windows).
+(window_plan) and the three launches around a solver (solve_windows); and the
+same for whole signals with any mask (MaskWindowPlan, mask_window_plan,
+solve_windows_mask).
 """
 from dataclasses import dataclass
 
@@ -247,6 +249,137 @@ def solve_windows(sigs, plan, device, per_gap, solve):
                                plan.gap_len, plan.gap_off, plan.gap_tab, plan.a, plan.gana,
                                plan.gsyn, dbuf)
         hist = gaps if per_gap else hist
+        buf, iters = dbuf.cpu().numpy(), iters.cpu().numpy()
+        hist = hist.cpu().numpy() if hist is not None else None
+    out, at = [], 0
+    for _ in plan.wtypes:
+        out.append([])
+        for s in sigs:
+            out[-1].append(buf[at:at + len(s)].copy())
+            at += len(s)
+    return out, iters, hist
+
+
+# ---------------------------------------------------------------- any mask
+@dataclass
+class MaskWindowPlan:
+    """The tables of one window-wise call on whole signals with any mask
+    (ainp_janssen_windows_mask / ainp_janssen_ola_mask).  Signals lie end to end
+    in one buffer, once per window shape (shape-major); signal i is padded to
+    the circular length L_i and has S_i = L_i / a windows whatever its mask.
+    One row per window that holds some, not all, missing samples: first the
+    rows whose missing samples are one run in window order (rows [0, n_one),
+    gap_start / gap_len), then the rows with a list (gap_len 0, miss_off /
+    miss_idx); within each part by shape, signal and window.  One run entry
+    per (shape, signal, run of missing samples of the signal)."""
+    wtypes: tuple
+    w: int
+    a: int
+    total: int
+    gana: np.ndarray          # [n_shapes, w]
+    gsyn: np.ndarray
+    missing: np.ndarray       # uint8 [total], 1 on a missing sample
+    sig_off: np.ndarray       # int64 [n_rows]
+    row_tab: np.ndarray       # int32 [n_rows, 4]: sig_len, L, window, shape
+    n_one: int
+    gap_start: np.ndarray     # int32 [n_rows], relative to the window
+    gap_len: np.ndarray
+    miss_off: np.ndarray      # int32 [n_rows + 1]
+    miss_idx: np.ndarray      # int32, window positions, ascending per row
+    win_row: np.ndarray       # int32: per (shape, signal) the row of each window, -1: none
+    run_off: np.ndarray       # int64 [n_runs]
+    run_tab: np.ndarray       # int32 [n_runs, 5]: h, c0, L, tab0, shape
+    run_signal: np.ndarray    # int32 [n_runs]
+
+    def __len__(self):
+        return len(self.sig_off)
+
+    def lists(self):
+        """The missing lists of the rows [n_one, n_rows)."""
+        return [self.miss_idx[self.miss_off[r]:self.miss_off[r + 1]]
+                for r in range(self.n_one, len(self))]
+
+
+def mask_window_plan(keys, w, a, pairs, masks, rows):
+    """The MaskWindowPlan of `rows`: per signal the (window, missing positions
+    in the window, ascending) of every window with a row, in window order."""
+    starts = np.concatenate(([0], np.cumsum([len(m) for m in masks]))).astype(np.int64)
+    per_shape = int(starts[-1])
+    Ls = [_cdiv(len(m), a) * a + (_cdiv(w, a) - 1) * a for m in masks]
+    one, many = [], []
+    for k in range(len(keys)):
+        for i, sig_rows in enumerate(rows):
+            for n, where in sig_rows:
+                run = int(where[-1]) - int(where[0]) + 1 == len(where)
+                (one if run else many).append((k, i, n, where))
+    order = one + many
+    # the window-to-row table of (shape k, signal i) starts at tab0[k * len(masks) + i]
+    tab0 = np.concatenate(([0], np.cumsum([L // a for L in Ls] * len(keys)))).astype(np.int64)
+    win_row = np.full(int(tab0[-1]), -1, np.int32)
+    for r, (k, i, n, _) in enumerate(order):
+        win_row[tab0[k * len(masks) + i] + n] = r
+    run_off, run_tab, run_signal = [], [], []
+    for k in range(len(keys)):
+        for i, m in enumerate(masks):
+            for g0, g1 in find_gaps(m):
+                run_off.append(k * per_shape + int(starts[i]) + g0)
+                run_tab.append((g1 - g0, g0, Ls[i], int(tab0[k * len(masks) + i]), k))
+                run_signal.append(i)
+    i32 = lambda v, cols=None: np.array(v, dtype=np.int32).reshape((-1,) if cols is None
+                                                                  else (-1, cols))
+    lists = [np.zeros(0, np.int32)] * len(one) + [np.asarray(wh, np.int32) for *_, wh in many]
+    miss_off = np.zeros(len(order) + 1, np.int32)
+    np.cumsum([len(v) for v in lists], out=miss_off[1:])
+    missing = np.concatenate([~np.asarray(m, bool) for m in masks]) if masks else np.zeros(0, bool)
+    return MaskWindowPlan(
+        tuple(keys), w, a, per_shape * len(keys),
+        np.stack([g for g, _ in pairs]), np.stack([g for _, g in pairs]),
+        np.tile(missing.astype(np.uint8), len(keys)),
+        np.array([k * per_shape + int(starts[i]) for k, i, _, _ in order], dtype=np.int64),
+        i32([(len(masks[i]), Ls[i], n, k) for k, i, n, _ in order], 4), len(one),
+        i32([wh[0] for *_, wh in one] + [0] * len(many)),
+        i32([len(wh) for *_, wh in one] + [0] * len(many)),
+        miss_off, np.concatenate(lists) if lists else np.zeros(0, np.int32), win_row,
+        np.array(run_off, dtype=np.int64), i32(run_tab, 5), i32(run_signal))
+
+
+def solve_windows_mask(sigs, plan, device, solve_runs, solve_lists):
+    """The launches of a window-wise call on whole signals: the signals, end to
+    end once per shape, and their byte mask go to the device;
+    ops.janssen_windows_mask gathers the rows; solve_runs(sol[:n_one]) and
+    solve_lists(sol[n_one:]) -> (iters, history or None) solve the two parts in
+    place, each at most once; ops.janssen_ola_mask adds them back and turns the
+    rows' history into the runs'.  -> (per shape the per-signal results, iters
+    per row, history per run or None) as numpy.  A plan without rows launches
+    nothing: its missing samples belong to windows that are all missing and
+    stay zero; the history is None."""
+    import torch
+    from . import ops
+    buf = np.concatenate([s for _ in plan.wtypes for s in sigs]) if sigs else np.zeros(0)
+    iters, hist = np.zeros(0, np.int32), None
+    if len(plan):
+        dbuf = torch.from_numpy(buf).to(device)
+        sol = ops.janssen_windows_mask(dbuf, torch.from_numpy(plan.missing).to(device),
+                                       plan.sig_off, plan.row_tab, plan.w, plan.a, plan.gana)
+        parts = []
+        if plan.n_one:
+            parts.append(solve_runs(sol[:plan.n_one]))
+        if plan.n_one < len(plan):
+            parts.append(solve_lists(sol[plan.n_one:]))
+        iters = torch.cat([it for it, _ in parts])
+        row_hist = None
+        if parts[0][1] is not None:
+            # the two solvers' histories side by side, NaN beyond a row's list
+            row_hist = torch.full((len(plan), parts[0][1].shape[1],
+                                   max(h.shape[2] for _, h in parts)), float("nan"),
+                                  device=sol.device, dtype=torch.float64)
+            at = 0
+            for _, h in parts:
+                row_hist[at:at + h.shape[0], :, :h.shape[2]] = h
+                at += h.shape[0]
+        hist = ops.janssen_ola_mask(sol, row_hist, plan.row_tab, plan.gap_start, plan.gap_len,
+                                    plan.miss_off, plan.miss_idx, plan.win_row, plan.run_off,
+                                    plan.run_tab, plan.a, plan.gana, plan.gsyn, dbuf)
         buf, iters = dbuf.cpu().numpy(), iters.cpu().numpy()
         hist = hist.cpu().numpy() if hist is not None else None
     out, at = [], 0

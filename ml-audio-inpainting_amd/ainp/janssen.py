@@ -16,7 +16,11 @@ cuts with offset.m and min_sig_supp_2.m; Hann, rectangular and Tukey windows)
 are plan_windows / janssen_windowed at the end of the file: every window with
 missing samples, of every gap, signal and window shape, is one row of the same
 ainp_janssen_ex launch, between the gather and the overlap-add of
-csrc/janssen_windows.hip.
+csrc/janssen_windows.hip.  plan_windows_mask / janssen_windowed_mask after them
+are segmentation_inp.m on a whole signal with any mask: one window grid per
+signal, windows with one run of missing samples to ainp_janssen_ex, the others
+to ainp_janssen_mask, between the any-mask gather and overlap-add of the same
+file.
 """
 from __future__ import annotations
 
@@ -24,9 +28,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .gaps import (WTYPES, WindowPlan, _cdiv, _normalise, _to_numpy, check_shift,  # noqa: F401
-                   find_gaps, gap_sdr, restack, solve_windows, window_pair, window_pairs,
-                   window_plan, window_rescale, window_rows, wtype_key)
+from .gaps import (WTYPES, MaskWindowPlan, WindowPlan, _cdiv, _normalise,  # noqa: F401
+                   _to_numpy, check_shift, find_gaps, gap_sdr, mask_window_plan, restack,
+                   solve_windows, solve_windows_mask, window_pair, window_pairs, window_plan,
+                   window_rescale, window_rows, wtype_key)
 
 P_MAX = 3072          # csrc/ar_limits.h JN_PMAX
 N_MAX = 16384         # JN_NMAX
@@ -382,6 +387,106 @@ def janssen_windowed(signal, mask=None, p=512, w=4096, a=1024, wtype="hann", max
                               "end": int(plan.gap_range[g, 1]),
                               "iters": [int(v) for v in iters[row0:row0 + nrows]],
                               "history": hist[g, :, :h].copy() if hist is not None else None})
+    out = {}
+    for k, r in zip(keys, res):
+        r = restack(r, kind)
+        out[k] = (r, info[k]) if return_history else r
+    return out[keys[0]] if single else out
+
+
+# -------------------------------------------------- window-wise, any mask
+# utils/segmentation_inp.m as it is written: called on a whole signal with any
+# NaN pattern, one fixed grid of windows, no per-gap support.
+def plan_windows_mask(masks, p=512, w=4096, a=1024, wtypes=("hann",)):
+    """The batch layout of the window-wise algorithm on whole signals for a
+    list of boolean observed masks of any pattern and a sequence of window
+    shapes.  Signal i of n samples is padded to L = ceil(n / a) a + (w / a - 1) a
+    and window s < L / a holds the circular indices (s a - floor(w / 2) + j) mod
+    L; every window with some, not all, samples missing is a row, whatever the
+    number of runs they form (a set split by the wrap counts as two runs).
+    ValueError for what is not covered: what plan_windows refuses for w, a and
+    p (a not dividing w, w / a < 2, w not in (p, 16384]), an overlap-add weight
+    that is not positive, a window that holds more than 2048 missing samples.
+    A run may be longer than w or than 2048: the windows inside it have no row."""
+    w, a, p = int(w), int(a), int(p)
+    check_shift(w, a)
+    if not p < w <= W_MAX:
+        raise ValueError(f"w must be in (p, {W_MAX}], got w = {w}, p = {p}")
+    keys = tuple(wtype_key(t) for t in wtypes)
+    if not keys or len(set(keys)) != len(keys):
+        raise ValueError("wtype needs at least one shape, each once")
+    pairs = window_pairs(keys, w, a)
+    pos = np.arange(w)
+    rows = []
+    for i, obs in enumerate(masks):
+        n = len(obs)
+        L = _cdiv(n, a) * a + (_cdiv(w, a) - 1) * a
+        miss = np.zeros(L, bool)
+        miss[:n] = ~np.asarray(obs, bool)
+        # missing samples per window from one prefix sum over the circle
+        csum = np.concatenate(([0], np.cumsum(np.concatenate((miss, miss[:w])))))
+        first = (np.arange(L // a) * a - w // 2) % L
+        count = csum[first + w] - csum[first]
+        if count.max(initial=0) > GAP_MAX:
+            s = int(np.argmax(count))
+            raise ValueError(f"signal {i}: window {s} holds {int(count[s])} missing samples, at "
+                             f"most {GAP_MAX}")
+        rows.append([(int(s), np.flatnonzero(miss[(first[s] + pos) % L]).astype(np.int32))
+                     for s in np.flatnonzero((count > 0) & (count < w))])
+    return mask_window_plan(keys, w, a, pairs, masks, rows)
+
+
+def janssen_windowed_mask(signal, mask=None, p=512, w=4096, a=1024, wtype="hann", maxit=20,
+                          method="lpc", return_history=False, device="cuda"):
+    """Fill the missing samples of `signal`, in any pattern, by the window-wise
+    Janssen algorithm on the GPU as the reference's segmentation_inp.m does on
+    a whole signal: one grid of windows of w samples every a samples, anchored
+    at the first sample and the same whatever the mask, every window with
+    missing samples inpainted by Janssen (any number of gaps in it),
+    overlap-added and rescaled.  It takes what janssen_windowed refuses --
+    several gaps in one window, scattered samples -- and does not use train.m's
+    per-gap supports, so its result is not janssen_windowed's.
+
+    Input layouts, mask / NaN conventions, wtype (a string, or a sequence of
+    shapes: a dict comes back), method and the return layout are
+    janssen_windowed's; only missing samples are written.  Windows whose
+    missing samples are one run go to ops.janssen (the Toeplitz solver), all
+    others to ops.janssen_mask, one launch each.  The history is one dict per
+    run of missing samples of the signal (signal, start, end, iters:
+    iterations completed by each window with a row that covers the run, in
+    ascending window order, history [maxit, end - start]: the run after every
+    iteration, NaN from the iteration on that one of its windows did not
+    complete).  ValueError: see plan_windows_mask.
+    """
+    from . import ops
+    check_args(p, maxit)
+    method_id(method)
+    single = isinstance(wtype, str)
+    shapes = (wtype,) if single else tuple(wtype)
+    sigs, masks, kind = _normalise(signal, mask)
+    plan = plan_windows_mask(masks, p, w, a, shapes)
+    keys = plan.wtypes
+    full = lambda rows: np.full(rows, plan.w)
+    res, iters, hist = solve_windows_mask(
+        sigs, plan, device,
+        lambda sol: ops.janssen(sol, full(plan.n_one), plan.gap_start[:plan.n_one],
+                                plan.gap_len[:plan.n_one], p, maxit,
+                                return_history=return_history, method=method),
+        lambda sol: ops.janssen_mask(sol, full(len(plan) - plan.n_one), plan.lists(), p, maxit,
+                                     return_history=return_history, method=method))
+    info = {k: [] for k in keys}
+    for g in range(len(plan.run_off)):
+        h, c0, L, tab0, k = (int(v) for v in plan.run_tab[g])
+        # the windows that hold a sample of the run, ascending
+        S = L // plan.a
+        lo, hi = _cdiv(c0 + plan.w // 2 - plan.w + 1, plan.a), (c0 + h - 1 + plan.w // 2) // plan.a
+        cover = sorted({s % S for s in range(lo, hi + 1)})
+        rows = [int(r) for r in plan.win_row[tab0:tab0 + S][cover] if r >= 0]
+        history = None
+        if return_history:
+            history = hist[g, :, :h].copy() if hist is not None else np.zeros((int(maxit), h))
+        info[keys[k]].append({"signal": int(plan.run_signal[g]), "start": c0, "end": c0 + h,
+                              "iters": [int(iters[r]) for r in rows], "history": history})
     out = {}
     for k, r in zip(keys, res):
         r = restack(r, kind)

@@ -2381,6 +2381,126 @@ def janssen_ola(sol, row_history, row_tab, gap_start, gap_len, gap_off, gap_tab,
     return hist
 
 
+def _mask_row_table(nrows, w, a, row_tab, n_shapes):
+    """The host checks of the rows of the two any-mask launches -> row_tab as
+    int32 numpy [n_rows, 4]: sig_len, L, window, shape."""
+    w, a = int(w), int(a)
+    if a < 1 or w % a or w // a < 2 or not 2 <= w <= _jn.W_MAX:
+        raise ValueError(f"a must divide w, w / a >= 2 and 2 <= w <= {_jn.W_MAX}")
+    rt = np.ascontiguousarray(np.asarray(row_tab, dtype=np.int32).reshape(-1, 4))
+    if len(rt) != nrows:
+        raise ValueError("row_tab needs one entry per row")
+    sig_len, L, win, shape = rt.T.astype(np.int64)
+    if nrows and not (np.all(L >= w) and np.all(L % a == 0) and np.all(sig_len >= 0)
+                      and np.all(sig_len <= L) and np.all(win >= 0) and np.all(win * a < L)
+                      and np.all(shape >= 0) and np.all(shape < n_shapes)):
+        raise ValueError("row_tab describes a window outside its support")
+    return rt
+
+
+def janssen_windows_mask(signals, missing, sig_off, row_tab, w, a, gana):
+    """ainp_janssen_windows_mask: cut the windows of the window-wise Janssen
+    algorithm out of whole signals with any pattern of missing samples.
+    signals: flat float64 cuda buffer, every signal end to end; missing: uint8
+    cuda buffer laid out like it, non-zero on a missing sample; the tables (host
+    integers, checked here) and gana [n_shapes, w] (host float64) as
+    include/ainp.h describes them.  Returns sol [n_rows, w] float64: signal *
+    gana, zeros on the missing samples and on the padding."""
+    _req(signals, "signals", dtype=torch.float64)
+    _req(missing, "missing", dtype=torch.uint8)
+    if signals.dim() != 1 or signals.numel() < 1 or missing.shape != signals.shape:
+        raise ValueError("signals must be one flat, non-empty buffer and missing one byte per "
+                         "sample of it")
+    gana = np.ascontiguousarray(gana, dtype=np.float64)
+    if gana.ndim != 2 or gana.shape[1] != int(w):
+        raise ValueError("the windows must be [n_shapes, w]")
+    so = np.asarray(sig_off, dtype=np.int64).reshape(-1)
+    nrows = len(so)
+    rt = _mask_row_table(nrows, w, a, row_tab, gana.shape[0])
+    if nrows and not (np.all(so >= 0) and np.all(so + rt[:, 0] <= signals.numel())):
+        raise ValueError("row_tab describes a signal outside the buffer")
+    dv = signals.device
+    sol = torch.empty(nrows, int(w), device=dv, dtype=torch.float64)
+    if nrows:
+        _T.janssen_windows_mask(signals, missing, torch.from_numpy(so).to(dv), _dev_i32(rt, dv),
+                                int(a), torch.from_numpy(gana).to(dv), sol)
+    return sol
+
+
+def janssen_ola_mask(sol, row_history, row_tab, gap_start, gap_len, miss_off, miss_idx, win_row,
+                     run_off, run_tab, a, gana, gsyn, signals):
+    """ainp_janssen_ola_mask: overlap-add the solved windows `sol` [n_rows, w]
+    back into the runs of missing samples of `signals` (flat float64 cuda
+    buffer, written on the missing samples only) and divide by the window
+    weight; a run's rows are found through win_row.  row_history: the rows'
+    history [n_rows, maxit, longest list] in the order of their missing lists,
+    or None; with it returns history [n_runs, maxit, max h] float64 (NaN beyond
+    a run's h), else None.  Tables as include/ainp.h describes them, host
+    integers checked here: gap_len[r] >= 1 for a row of one run, 0 for a row
+    whose list is miss_idx[miss_off[r]:miss_off[r + 1]]."""
+    _req(sol, "sol", dtype=torch.float64)
+    _req(signals, "signals", dtype=torch.float64)
+    if sol.dim() != 2 or signals.dim() != 1 or signals.numel() < 1:
+        raise ValueError("sol must be [n_rows, w] and signals one flat, non-empty buffer")
+    nrows, w = sol.shape
+    total = signals.numel()
+    gana = np.ascontiguousarray(gana, dtype=np.float64)
+    gsyn = np.ascontiguousarray(gsyn, dtype=np.float64)
+    if gana.ndim != 2 or gana.shape[1] != w or gsyn.shape != gana.shape:
+        raise ValueError("gana and gsyn must both be [n_shapes, w]")
+    rt = _mask_row_table(nrows, w, a, row_tab, gana.shape[0])
+    gs = np.asarray(gap_start, dtype=np.int64).reshape(-1)
+    gl = np.asarray(gap_len, dtype=np.int64).reshape(-1)
+    mo = np.asarray(miss_off, dtype=np.int64).reshape(-1)
+    mi = np.asarray(miss_idx, dtype=np.int64).reshape(-1)
+    if not (len(gs) == len(gl) == nrows and len(mo) == nrows + 1):
+        raise ValueError("gap_start and gap_len need one entry per row, miss_off one more")
+    cnt = np.diff(mo)
+    if not (mo[0] >= 0 and np.all(cnt >= 0) and mo[-1] <= len(mi)):
+        raise ValueError("miss_off must ascend from >= 0 to <= len(miss_idx)")
+    one = gl >= 1
+    if not (np.all(gl >= 0) and np.all(gl <= _jn.GAP_MAX) and np.all(gs[one] >= 0)
+            and np.all((gs + gl)[one] <= w) and np.all(cnt[one] == 0)
+            and np.all(cnt[~one] >= 1) and np.all(cnt <= _jn.GAP_MAX)):
+        raise ValueError(f"every row has one run inside its window (1 <= gap_len <= "
+                         f"{_jn.GAP_MAX}) or gap_len 0 and a list of 1 .. {_jn.GAP_MAX} samples")
+    for r in np.flatnonzero(~one):
+        v = mi[mo[r]:mo[r + 1]]
+        if not (v[0] >= 0 and v[-1] < w and np.all(np.diff(v) > 0)):
+            raise ValueError(f"row {r}: the missing samples must ascend strictly inside [0, {w})")
+    wr = np.asarray(win_row, dtype=np.int64).reshape(-1)
+    if not (np.all(wr >= -1) and np.all(wr < nrows)):
+        raise ValueError("win_row names a row that does not exist")
+    ro = np.asarray(run_off, dtype=np.int64).reshape(-1)
+    ru = np.ascontiguousarray(np.asarray(run_tab, dtype=np.int32).reshape(-1, 5))
+    if len(ro) != len(ru):
+        raise ValueError("run_off and run_tab need one entry per run")
+    nruns = len(ro)
+    h, c0, L, tab0, shape = ru.T.astype(np.int64)
+    if nruns and not (np.all(h >= 1) and np.all(c0 >= 0) and np.all(c0 + h <= L)
+                      and np.all(L >= w) and np.all(L % int(a) == 0) and np.all(tab0 >= 0)
+                      and np.all(tab0 + L // int(a) <= len(wr)) and np.all(shape >= 0)
+                      and np.all(shape < gana.shape[0]) and np.all(ro >= 0)
+                      and np.all(ro + h <= total)):
+        raise ValueError("run_tab describes a run outside its support, win_row or the buffer")
+    dv = sol.device
+    hist = None
+    if row_history is not None:
+        _req(row_history, "row_history", dtype=torch.float64)
+        if row_history.dim() != 3 or row_history.shape[0] != nrows:
+            raise ValueError("row_history must be [n_rows, maxit, longest list]")
+        hist = torch.full((nruns, row_history.shape[1], int(h.max()) if nruns else 0),
+                          float("nan"), device=dv, dtype=torch.float64)
+    if nruns:
+        up = lambda t: torch.from_numpy(t).to(dv)
+        _T.janssen_ola_mask(sol, row_history, _dev_i32(rt, dv), _dev_i32(gs, dv),
+                            _dev_i32(gl, dv), _dev_i32(mo, dv),
+                            _dev_i32(mi if len(mi) else np.zeros(1), dv), _dev_i32(wr, dv),
+                            up(ro), _dev_i32(ru, dv), int(h.max()), int(a), up(gana), up(gsyn),
+                            signals, hist)
+    return hist
+
+
 # ================================================================== SPAIN
 def _spain_rows(sol, gap_start, gap_len):
     """The checks of sol [n_rows, w] and the rows' runs that the two window

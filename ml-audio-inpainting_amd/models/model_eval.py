@@ -225,6 +225,24 @@ def run_janssen_mask_evaluation(input_dir, output_dir, gaps=((2.0, 0.08),), p=51
         gaps=tuple((float(s), float(g)) for s, g in gaps))
 
 
+def run_janssen_windowed_mask_evaluation(input_dir, output_dir, gaps=((2.0, 0.08),), p=512,
+                                         w=4096, a=1024, wtype="hann", maxit=20, method="lpc"):
+    """run_janssen_mask_evaluation for the window-wise algorithm on the whole
+    clip: janssen_windowed_mask fills a list of (start_s, length_s) gaps per
+    clip, however many of them one window sees, with windows of shape wtype
+    ("hann", "rect" or "tukey") of w samples every a samples.  Each result is
+    written as <stem>_janssen_<wtype>_mask[_arburg]_inpainted.flac.  Returns
+    {filename: SDR over all missing samples in dB}."""
+    from models.AudioReg import janssen_windowed_mask
+    from ainp.janssen import method_id, wtype_key
+    key = wtype_key(wtype)
+    return _evaluate_gap_filler(
+        input_dir, output_dir, f"janssen_{key}_mask" + ("_arburg" if method_id(method) else ""),
+        lambda clean, masks: janssen_windowed_mask(clean, masks, p=p, w=w, a=a, wtype=key,
+                                                   maxit=maxit, method=method),
+        gaps=tuple((float(s), float(g)) for s, g in gaps))
+
+
 AR_ALGORITHMS = ("extrapolation", "janssen", "janssen_hann", "janssen_rect", "janssen_tukey")
 
 
