@@ -207,6 +207,67 @@ int64_t ainp_resample_out_len(int64_t n_in, int up, int down);
  * *plan zeroed) for a ratio it refuses. */
 int ainp_resample_plan_query(int up, int down, int dtype, AinpResamplePlan* plan);
 
+/* Gap-constrained Griffin-Lim: a phase for the frames that touch missing
+ * samples and new values for those samples only, csrc/gap_phase.hip (the
+ * blind counterpart of utils.spectrogram_to_audio(..., phase=original_phase)
+ * in models/model_eval.py).  Frames are librosa's (center, zero padding,
+ * T = 1 + n_samples / hop), the window periodic Hann of win_length samples
+ * centre-padded to n_fft as for ainp_stft.  Frame t is unreliable when one of
+ * the win_length samples under its window is missing; padding is reliable.  A
+ * maximal set of consecutive unreliable frames is a run, one independent
+ * problem and one workgroup.  With y = x (missing samples: the value passed,
+ * NaN read as 0), for k = 0 .. n_iter - 1 over the frames U of the run, all in
+ * float64:
+ *   C = STFT_U(y);  resid[k] = sqrt(sum_t sum_f c_f (|C| - A)^2), c_f = 1 for
+ *   DC and Nyquist, else 2;  a = C - momentum / (1 + momentum) tprev (not at
+ *   k = 0);  tprev = C;  ang = a / (|a| + DBL_MIN);  f_t = irfft(A ang) w;
+ *   y[n] = sum_t f_t[n - t hop] / sum_t w^2[n - t hop] on the missing samples n
+ *   under a window of the run, summed over ascending t.
+ * Fixed summation order, no atomics: the same bits on every call.
+ *
+ * ainp_gap_phase_plan (host only; mask is a HOST array of n_samples bytes,
+ * 1 = reliable): writes the runs in ascending order, at most max_runs of them,
+ * and returns their number; AINP_EINVAL for n_fft not a power of two in
+ * [16, 2048], win_length outside [1, n_fft], hop < 1 or hop >= win_length (the
+ * steady-state window sum-square has a zero), n_samples > 2^31 - 1;
+ * AINP_EUNSUPPORTED for a run longer than the cap of csrc/gap_phase_plan.h
+ * (its span, the overlap-add numerator and one wave's transform no longer fit
+ * in 160 KB of LDS). */
+#define AINP_GP_LDS 0        /* tprev and the magnitudes of a run in LDS */
+#define AINP_GP_WORKSPACE 1  /* in the run's slice of the workspace, read through L2 */
+typedef struct AinpGapPhaseRun {
+  int64_t first_frame;
+  int64_t n_frames;
+  int64_t span_start; /* first sample of the span, first_frame hop - n_fft/2 (may be < 0) */
+  int64_t span;       /* (n_frames - 1) hop + n_fft samples */
+  int residency;      /* AINP_GP_*, of a launch whose longest run this is */
+  int waves;          /* waves of its workgroup, likewise */
+} AinpGapPhaseRun;
+int64_t ainp_gap_phase_plan(const uint8_t* mask, int64_t n_samples, int n_fft, int hop,
+                            int win_length, AinpGapPhaseRun* runs, int64_t max_runs);
+/* Bytes of workspace for a launch of n_runs runs, the longest of max_frames
+ * frames: 0 on AINP_GP_LDS (and for a refused shape). */
+size_t ainp_gap_phase_workspace(int64_t n_runs, int64_t max_frames, int n_fft, int hop);
+/* x, out [rows][n_samples] of dtype 0 = float32 or 1 = float64; out holds a
+ * copy of x on entry (it must not alias x) and only the missing samples under
+ * a window of a run are written, rounded once from float64.  mask uint8
+ * [rows][n_samples], 1 = reliable.  mag float32 [rows][n_fft/2 + 1][n_frames],
+ * linear magnitudes, n_frames = 1 + n_samples / hop.  Run r is frames
+ * [run_first[r], run_first[r] + run_frames[r]) of row run_row[r] (int32
+ * [n_runs], device, as ainp_gap_phase_plan finds them; a run outside its row
+ * or longer than max_frames is skipped by its workgroup).  window float64
+ * [n_fft].  resid float64 [n_runs][n_iter] or NULL.  n_iter in [1, 1000],
+ * momentum in [0, 1].  The plan is that of max_frames; workspace as
+ * ainp_gap_phase_workspace(n_runs, max_frames, ...).  n_runs == 0 is a no-op;
+ * every refusal of the plan query and any other bad argument is an error
+ * without a launch. */
+int ainp_gap_phase(const void* x, void* out, int dtype, int64_t rows, int64_t n_samples,
+                   const uint8_t* mask, const float* mag, int64_t n_frames,
+                   const int32_t* run_row, const int32_t* run_first, const int32_t* run_frames,
+                   int64_t n_runs, int64_t max_frames, const double* window, int n_fft, int hop,
+                   int win_length, int n_iter, double momentum, double* resid, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* Gap-wise Janssen autoregressive inpainting, the AR row of the reference's
  * model comparison (models/AudioReg/utils/janssen_inp.m, method "lpc", as
  * models/AudioReg/train.m drives it).  Float64 throughout.  sol

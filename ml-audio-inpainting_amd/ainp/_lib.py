@@ -54,6 +54,12 @@ class ResamplePlan(ctypes.Structure):
                                      "route")] + [("table_elems", c_int64), ("lds_bytes", c_int64)]
 
 
+class GapPhaseRun(ctypes.Structure):
+    """AinpGapPhaseRun (include/ainp.h)."""
+    _fields_ = [(n, c_int64) for n in ("first_frame", "n_frames", "span_start", "span")] + [
+        ("residency", c_int), ("waves", c_int)]
+
+
 _SIGS = {
     "ainp_abi_version": (c_int, []),
     "ainp_build_target": (c_char_p, []),
@@ -261,6 +267,13 @@ _SIGS = {
                                    P]),
     "ainp_resample_out_len": (c_int64, [c_int64, c_int, c_int]),
     "ainp_resample_plan_query": (c_int, [c_int, c_int, c_int, POINTER(ResamplePlan)]),
+    # gap-constrained Griffin-Lim and its host plan (csrc/gap_phase.hip, gap_phase_plan.h)
+    "ainp_gap_phase_plan": (c_int64, [P, c_int64, c_int, c_int, c_int, POINTER(GapPhaseRun),
+                                      c_int64]),
+    "ainp_gap_phase_workspace": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "ainp_gap_phase": (c_int, [P, P, c_int, c_int64, c_int64, P, P, c_int64, P, P, P, c_int64,
+                               c_int64, P, c_int, c_int, c_int, c_int, c_double, P, P, c_size_t,
+                               P]),
     # Janssen autoregressive gap inpainting (csrc/janssen.hip)
     "ainp_janssen": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "ainp_janssen_workspace": (c_size_t, [c_int64, c_int, c_int, c_int]),

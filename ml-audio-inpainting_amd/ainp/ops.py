@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import gap_phase as _gp
 from . import janssen as _jn
 from . import mel as _mel
 from . import resample as _rs
@@ -2149,6 +2150,51 @@ def resample_poly(x, up, down, n=None, out_len=None):
     out = torch.empty(rows, out_len, device=x.device, dtype=x.dtype)
     _T.resample_poly(x2, table, n_dev, int(up), int(down), out)
     return out.reshape(-1) if x.dim() == 1 else out
+
+
+# ============================================================== gap phase
+def gap_phase(x, mask, mag, run_row, run_first, run_frames, n_fft, hop_length, win_length=None,
+              n_iter=64, momentum=0.99, out=None, resid=None):
+    """ainp_gap_phase, one launch for every run of the batch: x [rows, S] float32
+    / float64 cuda, mask uint8 [rows, S] (1 = reliable), mag float32
+    [rows, n_fft/2+1, 1 + S // hop].  run_row / run_first / run_frames: the runs
+    of unreliable frames as ainp.gap_phase.plan_gap_phase_runs finds them (lists
+    or int32 cuda tensors; lists are checked against the rows here).  out: a
+    copy of x that receives the filled samples (default: made here); resid: an
+    optional float64 [runs, n_iter].  Returns out.  ainp.gap_phase.gap_phase_fill
+    is the checked entry point; this is the bare operator."""
+    _req(x, "x", dtype=None)
+    _req(mask, "mask", dtype=torch.uint8)
+    _req(mag, "mag")
+    win_length = n_fft if win_length is None else win_length
+    _gp.check_shape(n_fft, hop_length, win_length)
+    tabs = []
+    for name, t in (("run_row", run_row), ("run_first", run_first), ("run_frames", run_frames)):
+        tabs.append(_req(t, name, dtype=torch.int32).reshape(-1) if isinstance(t, torch.Tensor)
+                    else _dev_i32([int(v) for v in t], x.device))
+    n_runs = tabs[0].numel()
+    if isinstance(run_frames, torch.Tensor):
+        max_frames = int(run_frames.max()) if n_runs else 0
+    else:
+        max_frames = max((int(v) for v in run_frames), default=0)
+        T = 1 + x.shape[1] // hop_length
+        if any(not 0 <= int(r) < x.shape[0] for r in run_row) or any(
+                int(f) < 0 or int(n) < 1 or int(f) + int(n) > T
+                for f, n in zip(run_first, run_frames)):
+            raise ValueError("a run lies outside its row's frames")
+    if out is None:
+        out = x.clone()
+    if n_runs == 0:
+        return out
+    if _gp.run_plan(n_fft, hop_length, max_frames) is None:
+        raise ValueError(f"a run of {max_frames} frames is longer than the cap")
+    nbytes = int(_lib.lib.ainp_gap_phase_workspace(n_runs, max_frames, int(n_fft),
+                                                   int(hop_length)))
+    ws = torch.empty(-(-nbytes // 8), device=x.device, dtype=torch.float64) if nbytes else None
+    w = _device_window("hann", win_length, n_fft, x.device)
+    _T.gap_phase(x, mask, mag, tabs[0], tabs[1], tabs[2], max_frames, w, int(n_fft),
+                 int(hop_length), int(win_length), int(n_iter), float(momentum), resid, ws, out)
+    return out
 
 
 # ================================================================ Janssen

@@ -1,5 +1,6 @@
 // spain_fft.h — what the SPAIN kernels share (spain.hip, spain_omp.hip,
-// spain_learned.hip; basis_learn.hip takes the sum): the length-M real
+// spain_learned.hip; basis_learn.hip takes the sum; gap_phase.hip takes the
+// transform, one wave per frame with the wave-level barrier): the length-M real
 // transform as an M/2-point complex transform on split, skewed re / im arrays
 // in LDS with quarter-wave twiddles, the slots a lane holds of a half spectrum,
 // the fixed-order workgroup sum and the radix select with its tie rule.
@@ -53,9 +54,22 @@ struct SpFft {
   __device__ __forceinline__ int brev(int k) const { return (int)(__brev((unsigned)k) >> (32 - lgN)); }
 };
 
+// The transforms' barrier: the workgroup's, or (WAVE) the wave's own, for a
+// wave that transforms in arrays of its own with tid = its lane and NT = 64.
+template <bool WAVE>
+__device__ __forceinline__ void sp_barrier() {
+  if (WAVE) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else {
+    __syncthreads();
+  }
+}
+
 // In place, natural order in, bit-reversed order out.  Block size s: a at
 // b + j, c at b + j + s/2 become a + c and (a - c) W_s^j.  Ends on a barrier.
-template <int NT>
+template <int NT, bool WAVE = false>
 __device__ void sp_dif(const SpFft& f, int tid) {
   const int N = f.N, M = f.M;
   int s = N;
@@ -65,7 +79,7 @@ __device__ void sp_dif(const SpFft& f, int tid) {
       f.st(t, cadd(a, c));
       f.st(t + N / 2, cmul(csub(a, c), sp_tw(f.ct, 2 * t, M)));   // W_N^t = W_M^2t
     }
-    __syncthreads();
+    sp_barrier<WAVE>();
     s >>= 1;
   }
   for (; s >= 4; s >>= 2) {
@@ -83,13 +97,13 @@ __device__ void sp_dif(const SpFft& f, int tid) {
       f.st(i0 + 2 * q, cadd(t2, t3));
       f.st(i0 + 3 * q, cmul(csub(t2, t3), w2));
     }
-    __syncthreads();
+    sp_barrier<WAVE>();
   }
 }
 
 // The transpose: bit-reversed in, natural out, conjugate twiddles, no 1 / N.
 // a and c conj(W_s^j) become a + c and a - c.  Ends on a barrier.
-template <int NT>
+template <int NT, bool WAVE = false>
 __device__ void sp_dit(const SpFft& f, int tid) {
   const int N = f.N, M = f.M;
   const int top = (f.lgN & 1) ? N / 2 : N;
@@ -109,7 +123,7 @@ __device__ void sp_dit(const SpFft& f, int tid) {
       f.st(i0 + q, cadd(t1, e3));
       f.st(i0 + 3 * q, csub(t1, e3));
     }
-    __syncthreads();
+    sp_barrier<WAVE>();
   }
   if (f.lgN & 1) {
     for (int t = tid; t < N / 2; t += NT) {
@@ -117,7 +131,7 @@ __device__ void sp_dit(const SpFft& f, int tid) {
       f.st(t, cadd(a, c));
       f.st(t + N / 2, csub(a, c));
     }
-    __syncthreads();
+    sp_barrier<WAVE>();
   }
 }
 

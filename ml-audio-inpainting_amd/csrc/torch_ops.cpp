@@ -15,7 +15,7 @@
 // Host-only queries (workspace sizes, stat-part counts) and the FLAC codec
 // stay on the plain C ABI (ctypes); they launch nothing.  The resampler's two
 // (resample_out_len, resample_plan_query) are operators without tensor
-// arguments as well.
+// arguments as well, and gap_phase_plan is one over a host mask.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -264,6 +264,80 @@ std::vector<int64_t> resample_plan_query(int64_t up, int64_t down, int64_t dtype
   chk(ainp_resample_plan_query((int)up, (int)down, (int)dtype, &p), "resample_plan_query");
   return {p.up, p.down, p.half, p.taps, p.tpp, p.pitch, p.tile, p.span, p.route,
           p.table_elems, p.lds_bytes};
+}
+
+// -------------------------------------------------------------- gap phase
+void gap_phase(const Tensor& x, const Tensor& mask, const Tensor& mag, const Tensor& run_row,
+               const Tensor& run_first, const Tensor& run_frames, int64_t max_frames,
+               const Tensor& window, int64_t n_fft, int64_t hop, int64_t win_length,
+               int64_t n_iter, double momentum, const OptT& resid, const OptT& workspace,
+               const Tensor& out) {
+  GUARD(x);
+  TORCH_CHECK(x.dim() == 2, "x must be [rows, n_samples]");
+  TORCH_CHECK(n_fft >= 16 && n_fft <= 2048 && hop >= 1 && hop <= INT_MAX && win_length >= 1 &&
+                  win_length <= n_fft && n_iter >= INT_MIN && n_iter <= INT_MAX,
+              "gap_phase: n_fft in [16, 2048], hop >= 1, 1 <= win_length <= n_fft");
+  const bool f64 = x.scalar_type() == at::kDouble;
+  const at::ScalarType st = f64 ? at::kDouble : at::kFloat;
+  const int64_t rows = x.size(0), S = x.size(1), T = 1 + S / hop, n_runs = run_row.numel();
+  const void* xp = dev<void>(x, "x", st);
+  void* op = dev<void>(out, "out", st);
+  TORCH_CHECK(out.sizes() == x.sizes(), "out is ", out.sizes(), ", expected ", x.sizes());
+  TORCH_CHECK(mask.sizes() == x.sizes(), "mask is ", mask.sizes(), ", expected ", x.sizes());
+  TORCH_CHECK(mag.dim() == 3 && mag.size(0) == rows && mag.size(1) == n_fft / 2 + 1 &&
+                  mag.size(2) == T,
+              "mag is ", mag.sizes(), ", expected [", rows, ", ", n_fft / 2 + 1, ", ", T, "]");
+  for (const Tensor* t : {&out, &mask, &mag, &run_row, &run_first, &run_frames, &window})
+    same_device(x, *t);
+  numel_is(run_first, n_runs, "run_first");
+  numel_is(run_frames, n_runs, "run_frames");
+  numel_is(window, n_fft, "window");
+  double* rp = opt<double>(resid, "resid", at::kDouble);
+  if (rp) {
+    same_device(x, *resid);
+    numel_is(*resid, n_runs * n_iter, "resid");
+  }
+  void* wp = nullptr;
+  size_t wbytes = 0;
+  if (workspace.has_value() && workspace->defined()) {
+    TORCH_CHECK(workspace->is_cuda() && workspace->is_contiguous(),
+                "workspace must be a contiguous GPU tensor");
+    same_device(x, *workspace);
+    wp = workspace->data_ptr();
+    wbytes = (size_t)workspace->nbytes();
+  }
+  chk(ainp_gap_phase(xp, op, f64 ? 1 : 0, rows, S, dev<uint8_t>(mask, "mask", at::kByte),
+                     dev(mag, "mag"), T, dev<int32_t>(run_row, "run_row", at::kInt),
+                     dev<int32_t>(run_first, "run_first", at::kInt),
+                     dev<int32_t>(run_frames, "run_frames", at::kInt), n_runs, max_frames,
+                     dev<double>(window, "window", at::kDouble), (int)n_fft, (int)hop,
+                     (int)win_length, (int)n_iter, momentum, rp, wp, wbytes, stream_of(x)),
+      "gap_phase");
+}
+
+// host-only: the runs of a HOST mask [n_samples] uint8 as rows of (first_frame,
+// n_frames, span_start, span, residency, waves)
+Tensor gap_phase_plan(const Tensor& mask, int64_t n_fft, int64_t hop, int64_t win_length) {
+  TORCH_CHECK(mask.is_cpu() && mask.dim() == 1 && mask.scalar_type() == at::kByte &&
+                  mask.is_contiguous(),
+              "mask must be a contiguous CPU uint8 tensor [n_samples]");
+  TORCH_CHECK(n_fft >= INT_MIN && n_fft <= INT_MAX && hop >= INT_MIN && hop <= INT_MAX &&
+                  win_length >= INT_MIN && win_length <= INT_MAX,
+              "n_fft, hop and win_length must fit an int");
+  const uint8_t* mp = mask.data_ptr<uint8_t>();
+  const int64_t n = ainp_gap_phase_plan(mp, mask.numel(), (int)n_fft, (int)hop, (int)win_length,
+                                        nullptr, 0);
+  chk(n < 0 ? (int)n : 0, "gap_phase_plan");
+  std::vector<AinpGapPhaseRun> runs((size_t)std::max<int64_t>(n, 1));
+  ainp_gap_phase_plan(mp, mask.numel(), (int)n_fft, (int)hop, (int)win_length, runs.data(), n);
+  Tensor out = at::empty({n, 6}, at::kLong);
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int64_t i = 0; i < n; ++i) {
+    const AinpGapPhaseRun& r = runs[(size_t)i];
+    const int64_t v[6] = {r.first_frame, r.n_frames, r.span_start, r.span, r.residency, r.waves};
+    std::copy(v, v + 6, o + 6 * i);
+  }
+  return out;
 }
 
 // ---------------------------------------------------------------- Janssen
@@ -2309,6 +2383,11 @@ TORCH_LIBRARY(ainp, m) {
         "-> ()");
   m.def("resample_out_len(int n_in, int up, int down) -> int", &resample_out_len);
   m.def("resample_plan_query(int up, int down, int dtype) -> int[]", &resample_plan_query);
+  m.def("gap_phase(Tensor x, Tensor mask, Tensor mag, Tensor run_row, Tensor run_first, "
+        "Tensor run_frames, int max_frames, Tensor window, int n_fft, int hop, int win_length, "
+        "int n_iter, float momentum, Tensor(a!)? resid, Tensor? workspace, Tensor(b!) out) -> ()");
+  m.def("gap_phase_plan(Tensor mask, int n_fft, int hop, int win_length) -> Tensor",
+        &gap_phase_plan);
   m.def("janssen(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int maxit, "
         "Tensor(b!)? history, Tensor(c!) iters_done, Tensor? workspace, int method=0) -> ()");
   m.def("janssen_mask(Tensor(a!) sol, Tensor n, Tensor miss_off, Tensor miss_idx, int h_max, int p, "
@@ -2427,6 +2506,7 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("mel_fwd", &mel_fwd);
   m.impl("mel_inverse", &mel_inverse);
   m.impl("resample_poly", &resample_poly);
+  m.impl("gap_phase", &gap_phase);
   m.impl("janssen", &janssen);
   m.impl("janssen_mask", &janssen_mask);
   m.impl("ar_extrapolate", &ar_extrapolate);
@@ -2529,6 +2609,7 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("mel_fwd", torch::CppFunction::makeFallthrough());
   m.impl("mel_inverse", torch::CppFunction::makeFallthrough());
   m.impl("resample_poly", torch::CppFunction::makeFallthrough());
+  m.impl("gap_phase", torch::CppFunction::makeFallthrough());
   m.impl("janssen", torch::CppFunction::makeFallthrough());
   m.impl("janssen_mask", torch::CppFunction::makeFallthrough());
   m.impl("ar_extrapolate", torch::CppFunction::makeFallthrough());

@@ -17,6 +17,13 @@ Follows models/model_eval.py:23-227 step by step, on the MI355X kernels:
                 spectrogram_to_audio(..., phase=original phase) (:174-191);
                     -> save_audio (peak-normalised FLAC, native encoder)
   run_evaluation  (:198-227) every .flac of input_dir -> <name>_<type>_inpainted.flac
+  inpaint_blind             not in the reference: the same two models without
+                            the clean signal's phase -- features of the observed
+                            samples only, one forward pass, then the
+                            gap-constrained Griffin-Lim of ainp_gap_phase
+  run_blind_evaluation      every .flac through inpaint_blind ->
+                            <name>_<type>_blind_inpainted.flac and the gap SDRs,
+                            comparable with the rows below
   run_janssen_evaluation    the same clips and gap through the autoregressive
                             baseline (models/AudioReg; the third row of
                             models/AudioReg/model_eval.m's SDR table) ->
@@ -164,6 +171,117 @@ def run_evaluation(input_dir, output_dir, model_type, checkpoint, config_path):
         inpaint(model, config_path, os.path.join(input_dir, filename), out, device)
         outs.append(out)
     return outs
+
+
+def _missing_runs(observed):
+    """(start, length) of every run of missing samples of a bool mask."""
+    d = np.diff(np.concatenate(([0], (~np.asarray(observed, bool)).view(np.int8), [0])))
+    starts, ends = np.flatnonzero(d == 1), np.flatnonzero(d == -1)
+    return [(int(s), int(e - s)) for s, e in zip(starts, ends)]
+
+
+def blind_magnitudes(model, config_path, observed_audio, observed, sr=16000):
+    """The target magnitudes inpaint_blind hands to the phase step: features of
+    the zero-filled observed audio through the fused feature kernel
+    (ops.stft_features, each model's own frame-mask convention, as its dataset
+    builds them at training time), one forward pass, and the raw network output
+    taken to the linear domain -- expm1(max(out, 0)) for the GAN (trained on
+    log1p magnitudes), 10 ** out for the CNN-BLSTM (log10).  observed_audio
+    float32 cuda [S]; observed bool [S] (host).  Returns float32 cuda [F, T]."""
+    from ainp import ops
+    sp = load_config(config_path)["data"]["spectrogram"]
+    n_fft, hop, win = sp["n_fft"], sp["hop_length"], sp["win_length"]
+    gan = isinstance(model, PConvUNet)
+    if not gan and not isinstance(model, StackedBLSTMCNN):
+        raise ValueError("Unknown model type.")
+    x = (observed_audio * torch.from_numpy(np.asarray(observed, bool)).to(observed_audio.device)
+         ).to(torch.float32).reshape(1, -1).contiguous()
+    feat, fmask = None, None
+    for k, (gs, gl) in enumerate(_missing_runs(observed) or [(0, 0)]):
+        start = torch.tensor([gs], dtype=torch.int64, device=x.device)
+        if gan:
+            _, imp, _, m = ops.stft_features(x, start, gl, n_fft, hop, win, mode=ops.FEAT_GAN,
+                                             sample_rate=sr,
+                                             outputs=(False, k == 0, False, True))
+            feat = imp if k == 0 else feat
+            fmask = m if fmask is None else torch.minimum(fmask, m)     # 1 = valid
+        elif k == 0:     # the CNN-BLSTM's forward pass takes no mask
+            feat = ops.stft_features(x, start, gl, n_fft, hop, win, mode=ops.FEAT_CNNBLSTM,
+                                     sample_rate=sr, outputs=(True, False, False, False))[0]
+    F, T = feat.shape[-2:]
+    with torch.no_grad():
+        if gan:
+            out = model(feat[None], fmask[None]).reshape(F, T)
+            return torch.expm1(out.float().clamp_min(0.0)).contiguous()
+        out = model(feat.unsqueeze(1)).reshape(F, T)
+        return (10.0 ** out.float()).contiguous()
+
+
+def inpaint_blind(model, config_path, audio, mask, device, n_iter=64, momentum=0.99, init=None,
+                  sr=16000):
+    """Restore a gapped signal with either network without the phase of the
+    clean signal (not in the reference, whose inpaint() borrows it).
+
+    audio [S] (numpy or tensor; only the samples where mask is nonzero are
+    read), mask [S] nonzero = observed.  blind_magnitudes gives the target
+    magnitudes A from the observed samples alone; gap_phase_fill
+    (ainp_gap_phase) then finds a phase for the frames that touch the gap and
+    new values for the missing samples, n_iter iterations with `momentum`,
+    starting from zeros or, with init="janssen", from janssen_inpaint_mask's
+    fill.  Observed samples come back unchanged.  Returns float64 [S], numpy
+    for numpy input, else a tensor on `device`.
+
+    Deliberately not kept: the reference hands the GAN's log1p-domain output to
+    the ISTFT as if it were a magnitude (inpaint() keeps that).  Here A must be
+    commensurate with the STFT of the observed samples around the gap, so the
+    network output is always taken back to the linear domain first."""
+    from ainp.gap_phase import gap_phase_fill
+    if init not in (None, "janssen"):
+        raise ValueError(f"init must be None or 'janssen', got {init!r}")
+    as_numpy = not isinstance(audio, torch.Tensor)
+    observed = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask) != 0
+    x = torch.as_tensor(np.asarray(audio, np.float64) if as_numpy else audio).to(
+        device, torch.float64).reshape(-1)
+    obs_t = torch.from_numpy(observed).to(device)
+    x = torch.where(obs_t, x, torch.zeros_like(x))
+    if observed.all():
+        return x.cpu().numpy() if as_numpy else x
+    sp = load_config(config_path)["data"]["spectrogram"]
+    A = blind_magnitudes(model, config_path, x.float(), observed, sr=sr)
+    if init == "janssen":
+        from models.AudioReg import janssen_inpaint_mask
+        start = janssen_inpaint_mask([x.cpu().numpy()], [observed])[0]
+        x = torch.where(obs_t, x, torch.from_numpy(np.asarray(start, np.float64)).to(device))
+    y = gap_phase_fill(x, obs_t, A, sp["n_fft"], sp["hop_length"], sp["win_length"],
+                       n_iter=n_iter, momentum=momentum)
+    return y.cpu().numpy() if as_numpy else y
+
+
+def run_blind_evaluation(input_dir, output_dir, model_type, checkpoint, config_path,
+                         gaps=((GAP_START_S, GAP_LEN_S),), n_iter=64, momentum=0.99, init=None):
+    """run_evaluation without the clean phase: every .flac of input_dir gets the
+    gaps ((start_s, length_s) each; inpaint()'s one by default), goes through
+    inpaint_blind and is written as <stem>_<model_type>_blind_inpainted.flac.
+    Returns {filename: SDR over the missing samples in dB}, measured as
+    run_ar_evaluation and run_spain_evaluation measure theirs: like them the
+    model sees the observed samples only, so the rows compare."""
+    if not os.path.isdir(input_dir):
+        print(f"Error: Input directory not found: {input_dir}")
+        return
+    if not isinstance(checkpoint, dict) and not os.path.exists(checkpoint):
+        print(f"Error: Checkpoint file not found: {checkpoint}")
+        return
+    if not torch.cuda.is_available():
+        raise RuntimeError("model_eval runs on the MI355X kernels: no GPU visible")
+    device = torch.device("cuda")
+    model = load_model(model_type, config_path, checkpoint, device)
+
+    def fill(clean, masks):
+        return [inpaint_blind(model, config_path, c, m, device, n_iter=n_iter,
+                              momentum=momentum, init=init) for c, m in zip(clean, masks)]
+
+    return _evaluate_gap_filler(input_dir, output_dir, f"{model_type}_blind", fill,
+                                gaps=tuple((float(s), float(g)) for s, g in gaps))
 
 
 def _evaluate_gap_filler(input_dir, output_dir, suffix, fill,

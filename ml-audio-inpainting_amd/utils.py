@@ -330,6 +330,40 @@ def spectrogram_to_audio(spectrogram, phase=None, phase_info: bool = False, n_ff
     return y.cpu().numpy() if as_numpy else y
 
 
+def inpaint_phase(audio, mask, magnitude, n_fft=512, hop_length=None, win_length=None,
+                  n_iter=64, momentum=0.99, return_resid=False):
+    """Blind counterpart of spectrogram_to_audio(..., phase=original_phase) for
+    a gapped signal (not in the reference): fill the samples where `mask` is 0
+    so that the frames around them have the linear magnitudes `magnitude`
+    [n_fft/2+1, 1 + len // hop_length], by the gap-constrained Griffin-Lim of
+    ainp_gap_phase (ainp.gap_phase.gap_phase_fill; float64, deterministic, no
+    phase of the clean signal needed).  The observed samples come back
+    bit-identical; the values `audio` holds inside the gaps are the start.
+    hop_length defaults to win_length // 4.  [S] or [B, S]; numpy in -> numpy
+    out, a torch cuda tensor stays on the GPU."""
+    import torch
+    from ainp.gap_phase import gap_phase_fill
+    win_length = n_fft if win_length is None else win_length
+    hop_length = win_length // 4 if hop_length is None else hop_length
+    as_numpy = not isinstance(audio, torch.Tensor)
+    a = audio
+    if as_numpy:
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32 if a.dtype.itemsize <= 4 else np.float64)
+        a = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    m = torch.as_tensor(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask)
+    A = torch.as_tensor(np.asarray(magnitude) if not isinstance(magnitude, torch.Tensor)
+                        else magnitude).to(a.device, torch.float32)
+    res = gap_phase_fill(a, m.to(a.device), A, n_fft, hop_length, win_length, n_iter=n_iter,
+                         momentum=momentum, return_resid=return_resid)
+    if not as_numpy:
+        return res
+    if return_resid:
+        return res[0].cpu().numpy(), res[1].cpu().numpy()
+    return res.cpu().numpy()
+
+
 def extract_mel_spectrogram(audio_data, sample_rate: int = DEFAULT_SAMPLE_RATE,
                             n_fft: int = 2048, hop_length: int = 512, n_mels: int = 128,
                             fmin: float = 0.0, fmax: Optional[float] = None,
