@@ -268,6 +268,54 @@ int ainp_gap_phase(const void* x, void* out, int dtype, int64_t rows, int64_t n_
                    int win_length, int n_iter, double momentum, double* resid, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* Short-time objective intelligibility of a ragged batch, csrc/stoi.hip: STOI
+ * (Taal et al., IEEE TASL 19(7), 2011) or, with extended = 1, ESTOI (Jensen and
+ * Taal, IEEE/ACM TASLP 24(11), 2016), the intelligibility column beside the SDR
+ * of the reference's comparison table (models/AudioReg/train.m:183-213 scores
+ * every iteration of every method of every clip).  Signals are at 10 kHz,
+ * float64 throughout.  n_clean clean rows x [n_clean][stride] of n[c] samples
+ * and n_restored restored rows y [n_restored][stride], row r scored against
+ * clean row clean_row[r] (any order, repeats allowed) over that row's length.
+ * Frames of 256 samples every 128 under w[i] = 0.5 (1 - cos(2 pi (i + 1) / 257));
+ * a row of L samples has (L - 256) / 128 + 1 of them (0 for L < 256).  The
+ * clean row alone decides which frames stay: e[k] = 20 log10(|w x_k| + 2^-52)
+ * above max(e) - 40 dB.  The kept windowed frames of either signal are
+ * overlap-added 128 apart (no window-sum division), framed and windowed again,
+ * transformed at 512 points and summed into 15 one-third octave bands from
+ * 150 Hz (bins [7, 219)); 30-frame segments of the band envelopes give d_m by
+ * the measure's normalisation, and score[r] is their mean over the T - 29
+ * segments, or 1e-5 when the clean row keeps T < 30 frames.  frames[c] = T.
+ * All-zero rows score exactly 0.  Fixed summation order, no atomics: a row's
+ * bits do not depend on the batch or the launch.  DESIGN section 17 states the
+ * definition in full.
+ *
+ * n and clean_row are HOST arrays (int32), checked here before any launch;
+ * tables is the same data on the device, n then clean_row, n_clean +
+ * n_restored int32.  AINP_EINVAL, without a launch, for negative sizes,
+ * extended outside {0, 1}, a length outside [0, min(stride, 2^20)], a
+ * clean_row outside [0, n_clean), a workspace smaller than
+ * ainp_stoi_workspace(n_clean, n_restored, longest n) or a missing pointer.
+ * n_clean == 0 is a no-op.
+ *
+ * ainp_stoi_plan (host only): the limit, the frame count of max_len samples,
+ * the workspace layout and the LDS of the keep launch (csrc/stoi_plan.h);
+ * AINP_EINVAL (*plan zeroed) for negative counts or max_len over the limit. */
+typedef struct AinpStoiPlan {
+  int64_t max_len;   /* the row limit, 2^20 samples */
+  int64_t frames;    /* of a row of max_len samples */
+  int64_t t_stride;  /* frames of a row of the keep list and the envelopes */
+  int64_t chunks;    /* partial sums of a restored row, 64 segments each */
+  int64_t keep_off, env_off, part_off; /* byte offsets into the workspace */
+  int64_t bytes;     /* the workspace */
+  int64_t keep_lds;  /* dynamic LDS of the keep launch */
+} AinpStoiPlan;
+int ainp_stoi_plan(int64_t n_clean, int64_t n_restored, int64_t max_len, AinpStoiPlan* plan);
+size_t ainp_stoi_workspace(int64_t n_clean, int64_t n_restored, int64_t max_len);
+int ainp_stoi(const double* x, const double* y, int64_t stride, const int32_t* n,
+              int64_t n_clean, const int32_t* clean_row, int64_t n_restored,
+              const int32_t* tables, int extended, double* score, int32_t* frames,
+              void* workspace, size_t workspace_bytes, void* stream);
+
 /* Gap-wise Janssen autoregressive inpainting, the AR row of the reference's
  * model comparison (models/AudioReg/utils/janssen_inp.m, method "lpc", as
  * models/AudioReg/train.m drives it).  Float64 throughout.  sol

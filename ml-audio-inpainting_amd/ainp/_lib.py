@@ -60,6 +60,12 @@ class GapPhaseRun(ctypes.Structure):
         ("residency", c_int), ("waves", c_int)]
 
 
+class StoiPlan(ctypes.Structure):
+    """AinpStoiPlan (include/ainp.h)."""
+    _fields_ = [(n, c_int64) for n in ("max_len", "frames", "t_stride", "chunks", "keep_off",
+                                       "env_off", "part_off", "bytes", "keep_lds")]
+
+
 _SIGS = {
     "ainp_abi_version": (c_int, []),
     "ainp_build_target": (c_char_p, []),
@@ -274,6 +280,10 @@ _SIGS = {
     "ainp_gap_phase": (c_int, [P, P, c_int, c_int64, c_int64, P, P, c_int64, P, P, P, c_int64,
                                c_int64, P, c_int, c_int, c_int, c_int, c_double, P, P, c_size_t,
                                P]),
+    # STOI / ESTOI of a ragged batch and its host plan (csrc/stoi.hip, stoi_plan.h)
+    "ainp_stoi_plan": (c_int, [c_int64, c_int64, c_int64, POINTER(StoiPlan)]),
+    "ainp_stoi_workspace": (c_size_t, [c_int64, c_int64, c_int64]),
+    "ainp_stoi": (c_int, [P, P, c_int64, P, c_int64, P, c_int64, P, c_int, P, P, P, c_size_t, P]),
     # Janssen autoregressive gap inpainting (csrc/janssen.hip)
     "ainp_janssen": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "ainp_janssen_workspace": (c_size_t, [c_int64, c_int, c_int, c_int]),

@@ -29,6 +29,7 @@ from . import gap_phase as _gp
 from . import janssen as _jn
 from . import mel as _mel
 from . import resample as _rs
+from . import stoi as _st
 from . import spain as _sp
 
 # AINP_TORCH_OPS: another build of the same registration (e.g. the UBSan build
@@ -2195,6 +2196,44 @@ def gap_phase(x, mask, mag, run_row, run_first, run_frames, n_fft, hop_length, w
     _T.gap_phase(x, mask, mag, tabs[0], tabs[1], tabs[2], max_frames, w, int(n_fft),
                  int(hop_length), int(win_length), int(n_iter), float(momentum), resid, ws, out)
     return out
+
+
+# =========================================================== STOI / ESTOI
+def stoi(x, y, n, clean_row, extended=False):
+    """ainp_stoi: STOI (or, extended, ESTOI) of a ragged batch at 10 kHz, float64.
+    x [C, stride] clean rows and y [R, stride] restored rows, float64 cuda; n: the
+    clean rows' lengths, clean_row: the clean row each restored row is scored
+    against (host integers, any order, repeats allowed; a restored row is as
+    long as its clean row).  Returns (score float64 [R], frames int32 [C]: the
+    frames the silent-frame rule keeps; fewer than 30 give the score 1e-5).
+    ValueError before any launch for a row over ainp.stoi.MAX_LEN samples or
+    the stride, or a clean_row outside [0, C).  ainp.stoi.stoi is the entry point
+    that takes signals at any rate; this is the bare operator."""
+    _req(x, "x", dtype=torch.float64)
+    _req(y, "y", dtype=torch.float64)
+    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+        raise ValueError("x must be [C, stride] and y [R, stride]")
+    C, stride = x.shape
+    R = y.shape[0]
+    n_host = np.asarray(n, dtype=np.int64).reshape(-1)
+    row_host = np.asarray(clean_row, dtype=np.int64).reshape(-1)
+    if n_host.size != C or row_host.size != R:
+        raise ValueError(f"n needs {C} entries and clean_row {R}")
+    if C and (n_host.min() < 0 or n_host.max() > min(stride, _st.MAX_LEN)):
+        raise ValueError(f"every n must lie in [0, min(stride, {_st.MAX_LEN})]")
+    if R and (row_host.min() < 0 or row_host.max() >= C):
+        raise ValueError(f"every clean_row must lie in [0, {C})")
+    score = torch.empty(R, device=x.device, dtype=torch.float64)
+    frames = torch.zeros(C, device=x.device, dtype=torch.int32)
+    if C == 0:
+        return score, frames
+    n32 = torch.from_numpy(n_host.astype(np.int32))
+    row32 = torch.from_numpy(row_host.astype(np.int32))
+    tables = torch.cat((n32, row32)).to(x.device)
+    nbytes = int(_lib.lib.ainp_stoi_workspace(C, R, int(n_host.max())))
+    ws = torch.empty(max(1, -(-nbytes // 8)), device=x.device, dtype=torch.float64)
+    _T.stoi(x, y, n32, row32, tables, bool(extended), ws, score, frames)
+    return score, frames
 
 
 # ================================================================ Janssen

@@ -15,7 +15,8 @@
 // Host-only queries (workspace sizes, stat-part counts) and the FLAC codec
 // stay on the plain C ABI (ctypes); they launch nothing.  The resampler's two
 // (resample_out_len, resample_plan_query) are operators without tensor
-// arguments as well, and gap_phase_plan is one over a host mask.
+// arguments as well, gap_phase_plan is one over a host mask, and stoi_plan one
+// over three integers.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -338,6 +339,46 @@ Tensor gap_phase_plan(const Tensor& mask, int64_t n_fft, int64_t hop, int64_t wi
     std::copy(v, v + 6, o + 6 * i);
   }
   return out;
+}
+
+// ------------------------------------------------------------ STOI / ESTOI
+// x [C, stride], y [R, stride] float64; n [C] and clean_row [R] are HOST int32
+// tensors (checked by ainp_stoi before any launch), tables [C + R] the same on
+// the device; score [R] float64 and frames [C] int32 are written
+void stoi(const Tensor& x, const Tensor& y, const Tensor& n, const Tensor& clean_row,
+          const Tensor& tables, bool extended, const Tensor& workspace, const Tensor& score,
+          const Tensor& frames) {
+  GUARD(x);
+  TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && x.size(1) == y.size(1),
+              "x must be [clean rows, stride] and y [restored rows, stride], got ", x.sizes(),
+              " and ", y.sizes());
+  const int64_t C = x.size(0), R = y.size(0), stride = x.size(1);
+  for (const Tensor* t : {&n, &clean_row})
+    TORCH_CHECK(t->is_cpu() && t->scalar_type() == at::kInt && t->is_contiguous(),
+                "n and clean_row must be contiguous CPU int32 tensors");
+  numel_is(n, C, "n");
+  numel_is(clean_row, R, "clean_row");
+  numel_is(tables, C + R, "tables");
+  numel_is(score, R, "score");
+  numel_is(frames, C, "frames");
+  for (const Tensor* t : {&y, &tables, &workspace, &score, &frames}) same_device(x, *t);
+  TORCH_CHECK(workspace.is_cuda() && workspace.is_contiguous(),
+              "workspace must be a contiguous GPU tensor");
+  chk(ainp_stoi(dev<double>(x, "x", at::kDouble), dev<double>(y, "y", at::kDouble), stride,
+                n.data_ptr<int32_t>(), C, clean_row.data_ptr<int32_t>(), R,
+                dev<int32_t>(tables, "tables", at::kInt), extended ? 1 : 0,
+                dev<double>(score, "score", at::kDouble), dev<int32_t>(frames, "frames", at::kInt),
+                workspace.data_ptr(), (size_t)workspace.nbytes(), stream_of(x)),
+      "stoi");
+}
+
+// host-only: (max_len, frames, t_stride, chunks, keep_off, env_off, part_off,
+// bytes, keep_lds) of csrc/stoi_plan.h
+std::vector<int64_t> stoi_plan(int64_t n_clean, int64_t n_restored, int64_t max_len) {
+  AinpStoiPlan p;
+  chk(ainp_stoi_plan(n_clean, n_restored, max_len, &p), "stoi_plan");
+  return {p.max_len, p.frames, p.t_stride, p.chunks, p.keep_off, p.env_off, p.part_off,
+          p.bytes, p.keep_lds};
 }
 
 // ---------------------------------------------------------------- Janssen
@@ -2388,6 +2429,9 @@ TORCH_LIBRARY(ainp, m) {
         "int n_iter, float momentum, Tensor(a!)? resid, Tensor? workspace, Tensor(b!) out) -> ()");
   m.def("gap_phase_plan(Tensor mask, int n_fft, int hop, int win_length) -> Tensor",
         &gap_phase_plan);
+  m.def("stoi(Tensor x, Tensor y, Tensor n, Tensor clean_row, Tensor tables, bool extended, "
+        "Tensor workspace, Tensor(a!) score, Tensor(b!) frames) -> ()");
+  m.def("stoi_plan(int n_clean, int n_restored, int max_len) -> int[]", &stoi_plan);
   m.def("janssen(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int maxit, "
         "Tensor(b!)? history, Tensor(c!) iters_done, Tensor? workspace, int method=0) -> ()");
   m.def("janssen_mask(Tensor(a!) sol, Tensor n, Tensor miss_off, Tensor miss_idx, int h_max, int p, "
@@ -2507,6 +2551,7 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("mel_inverse", &mel_inverse);
   m.impl("resample_poly", &resample_poly);
   m.impl("gap_phase", &gap_phase);
+  m.impl("stoi", &stoi);
   m.impl("janssen", &janssen);
   m.impl("janssen_mask", &janssen_mask);
   m.impl("ar_extrapolate", &ar_extrapolate);
@@ -2610,6 +2655,7 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("mel_inverse", torch::CppFunction::makeFallthrough());
   m.impl("resample_poly", torch::CppFunction::makeFallthrough());
   m.impl("gap_phase", torch::CppFunction::makeFallthrough());
+  m.impl("stoi", torch::CppFunction::makeFallthrough());
   m.impl("janssen", torch::CppFunction::makeFallthrough());
   m.impl("janssen_mask", torch::CppFunction::makeFallthrough());
   m.impl("ar_extrapolate", torch::CppFunction::makeFallthrough());

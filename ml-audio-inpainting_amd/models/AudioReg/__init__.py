@@ -12,13 +12,16 @@ and S-SPAIN of references/spain (ainp/spain.py -> csrc/spain.hip between the
 same gather and overlap-add) and their whole-signal form with a learned
 unitary basis of references/basisopt (ainp/spain_learned.py ->
 csrc/spain_learned.hip), the basis itself learned as basis_opt_new.m learns it
-(ainp/basis_learn.py -> csrc/basis_learn.hip); and the gap SDR of train.m:196 /
-model_eval.m:60."""
+(ainp/basis_learn.py -> csrc/basis_learn.hip); the gap SDR of train.m:196 /
+model_eval.m:60; and, for the intelligibility column the reference fills with
+closed toolboxes, STOI / ESTOI of a batch and of every iteration of a Janssen
+history (ainp/stoi.py -> csrc/stoi.hip)."""
 from ainp.janssen import (ar_extrapolate, gap_sdr, janssen_inpaint, janssen_inpaint_mask,
                           janssen_windowed, janssen_windowed_mask, plan_mask_segments)
 from ainp.basis_learn import learn_basis, spain_learn_basis, spain_training_frames
 from ainp.spain import spain_inpaint
 from ainp.spain_learned import spain_learned_inpaint
+from ainp.stoi import stoi, stoi_curve
 
 __all__ = ["janssen_inpaint", "janssen_inpaint_mask", "plan_mask_segments", "janssen_windowed", "janssen_windowed_mask", "ar_extrapolate", "spain_inpaint", "gap_sdr",
-           "spain_learned_inpaint", "learn_basis", "spain_learn_basis", "spain_training_frames"]
+           "spain_learned_inpaint", "learn_basis", "spain_learn_basis", "spain_training_frames", "stoi", "stoi_curve"]

@@ -486,6 +486,46 @@ def export_48k_pairs(input_dir, reconstructed_dir, output_dir, suffix):
     return pairs
 
 
+def run_stoi_evaluation(input_dir, reconstructed_dir, suffix, extended=False):
+    """The intelligibility column of models/AudioReg/train.m:35-41 in place of
+    the closed PEMO-Q / PEAQ toolboxes: STOI (extended: ESTOI) of every
+    <stem>.flac of input_dir against its <stem>_<suffix>_inpainted.flac in
+    reconstructed_dir, paired as export_48k_pairs pairs them.  Each pair is
+    mixed to mono and truncated to the shorter of the two; all pairs of one
+    native rate are scored in one call (ainp.stoi.stoi: one resampling launch to
+    10 kHz, one scoring launch).  Returns {filename: score}."""
+    from ainp.stoi import stoi
+    if not os.path.isdir(input_dir):
+        print(f"Error: Input directory not found: {input_dir}")
+        return {}
+    if not torch.cuda.is_available():
+        raise RuntimeError("model_eval runs on the MI355X kernels: no GPU visible")
+    by_rate = {}      # native rate -> [(filename, clean, restored)]
+    for filename in sorted(f for f in os.listdir(input_dir) if f.lower().endswith(".flac")):
+        stem = os.path.splitext(filename)[0]
+        restored = os.path.join(reconstructed_dir, f"{stem}_{suffix}_inpainted.flac")
+        if not os.path.exists(restored):
+            continue
+        pair = []
+        for path in (os.path.join(input_dir, filename), restored):
+            try:
+                data, sr = utils._read_any(path)
+            except Exception as e:
+                raise IOError(f"Error loading audio file {path}: {str(e)}")
+            pair.append((data.mean(axis=1).astype(np.float64), int(sr)))
+        if pair[0][1] != pair[1][1]:
+            raise ValueError(f"{filename}: clean at {pair[0][1]} Hz, restored at {pair[1][1]} Hz")
+        n = min(len(pair[0][0]), len(pair[1][0]))
+        by_rate.setdefault(pair[0][1], []).append((filename, pair[0][0][:n], pair[1][0][:n]))
+    scores = {}
+    for sr, rows in by_rate.items():
+        got = stoi([c for _, c, _ in rows], [r for _, _, r in rows], fs=sr, extended=extended)
+        for (filename, _, _), v in zip(rows, got):
+            scores[filename] = float(v)
+            print(f"{filename}: {'ESTOI' if extended else 'STOI'} {v:.4f}")
+    return scores
+
+
 if __name__ == "__main__":
     # model_eval.py:229-256 (CNN-LSTM configuration by default)
     run_evaluation(input_dir=sys.argv[1] if len(sys.argv) > 1 else "../test_samples",
