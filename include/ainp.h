@@ -441,119 +441,81 @@ int ainp_ar_extrapolate(double* sol, int64_t n_segments, int64_t stride, const i
 size_t ainp_ar_extrapolate_workspace(int64_t n_segments, int n_max, int p, int gap_max,
                                      int method);
 
-/* Window-wise Janssen inpainting, the janssen_hann / janssen_rect /
- * janssen_tukey rows of the same comparison (utils/segmentation_inp.m as
- * train.m:146-172 drives it): two streams around ainp_janssen_ex.  Float64.
- * The support of a gap is sup_len samples of its signal from the signal index
- * `origin` (negative, or past the end: those samples read as observed zeros),
- * zero-padded to the circular length L = S * a.  Window s of S holds the
- * circular indices (s * a - floor(w / 2) + i) mod L, i = 0 .. w-1.  A window
- * with some, not all, samples missing is one row of the Janssen batch.
+/* Window-wise inpainting: the two streams around a window solver
+ * (ainp_janssen_ex, ainp_janssen_mask, ainp_spain, ainp_spain_omp), for the
+ * janssen_hann / janssen_rect / janssen_tukey rows of the same comparison
+ * (utils/segmentation_inp.m as train.m:146-172 drives it, one support per gap),
+ * for segmentation_inp.m called on a whole signal with any NaN pattern, and for
+ * spain_segmentation.m.  Float64; one gather and one overlap-add for all.
+ * A support is sup_len samples of its signal from the signal index `origin`
+ * (negative, or past the end: those samples read as observed zeros; a whole
+ * signal is its own support: origin 0, sup_len = sig_len), zero-padded to the
+ * circular length L = S * a.  Window s of S holds the circular indices
+ * (s * a - floor(w / 2) + i) mod L, i = 0 .. w-1.  A window with some, not all,
+ * samples missing is one row of the solver's batch (n = w), in any number of
+ * runs: rows of one run in window order are what ainp_janssen_ex and the SPAIN
+ * solvers take, the others go to ainp_janssen_mask.
+ *
+ * The tables.  signals: `total` float64 samples, every signal of the batch end
+ * to end; missing: `total` bytes laid out like it, non-zero on a missing
+ * sample.  Per row r: sig_off int64 [n_rows], where the row's signal starts in
+ * `signals`; row_tab int32 [n_rows][6]: sig_len, origin, sup_len, L, window
+ * index, shape; gap_start, gap_len int32 [n_rows]: gap_len[r] >= 1 for a row
+ * whose missing samples are the one run [gap_start[r], gap_start[r] +
+ * gap_len[r]) of the window, 0 for a row whose missing window positions are the
+ * strictly ascending list miss_idx[miss_off[r] .. miss_off[r + 1]) (miss_off
+ * int32 [n_rows + 1], miss_idx int32 [n_idx], n_idx >= 1).  Per unit g, one
+ * run of missing samples to write back: unit_off int64 [n_units], its first
+ * sample in `signals`; unit_tab int32 [n_units][5]: h (its samples; not limited
+ * to 2048), c0 (index of the first in its support), L, tab0, shape.  win_row
+ * int32 [n_tab]: win_row[tab0 + s] is the row of window s of the unit's support
+ * and shape, -1 for a window without a row -- with the wrap of the last windows
+ * to the head of a signal a unit's rows are not consecutive.  gana, gsyn
+ * [n_shapes][w]: the analysis and synthesis windows, made on the host.
  *
  * ainp_janssen_windows cuts the rows: sol[r][i] = signal sample * gana[shape][i],
- * zero on the row's missing run [gap_start[r], gap_start[r] + gap_len[r]), on
- * the padding and outside the signal.  signals: `total` float64 samples, every
- * signal of the batch end to end; sig_off int64 [n_rows]: where the row's
- * signal starts in it.  row_tab int32 [n_rows][6]: sig_len, origin, sup_len,
- * L, window index, shape.  gap_start, gap_len int32 [n_rows]: the tables
- * ainp_janssen_ex then takes (with n[r] = w).  gana [n_shapes][w]: the
- * analysis windows, made on the host.  Rows of any number of signals, gaps and
- * shapes go in one launch; a row whose entries contradict one another (L < w,
- * sup_len > L, window index * a >= L, shape >= n_shapes, a signal outside
- * [0, total)) is written as zeros.
+ * zero where missing[] is non-zero, on the padding and outside the signal.
+ * Rows of any number of signals, supports and shapes go in one launch; a row
+ * whose entries contradict one another (L < w, sup_len > L, window index * a >=
+ * L, shape >= n_shapes, a signal outside [0, total)) is written as zeros.
  *
- * ainp_janssen_ola puts the gaps back.  gap_off int64 [n_gaps]: the gap's
- * first sample in `signals`; gap_tab int32 [n_gaps][6]: h (missing samples),
- * c0 (support index of the first), L, row0, n_rows (its rows are row0 .. row0
- * + n_rows - 1, ascending window index), shape.  Per missing sample c = c0 + j:
- *   value = sum_rows sol[r][i_r] * gsyn[shape][i_r] / rescale,
- *   i_r = (c - win_r * a + floor(w / 2)) mod L   (rows with i_r < w only),
- *   rescale = sum_{s < L / a, i_s < w} gana[shape][i_s] * gsyn[shape][i_s],
- * both sums in ascending window order; rescale counts every window of the
- * support, also those with all samples missing, which have no row and add
- * zeros.  The value goes to signals[gap_off + j]; observed samples are never
- * written.  history (nullable) [n_gaps][maxit][out_stride]: the same from
- * row_history [n_rows][maxit][hist_stride], the history ainp_janssen_ex wrote
- * (hist_stride = its row length, the longest gap_len of the batch), for every
- * iteration; both or neither.  A NaN of row_history (an iteration a window did
- * not complete, where the caller prefilled with NaN) goes through the sum.
- * No atomics, fixed order: the same bits on every call.  A gap whose entries
- * contradict one another or reach outside `signals` is skipped.
+ * ainp_janssen_ola puts the units back, one lane per missing sample.  Per
+ * sample c = c0 + j
+ *   value = sum_s sol[win_row[tab0 + s]][i_s] * gsyn[shape][i_s] / rescale,
+ *   rescale = sum_s gana[shape][i_s] * gsyn[shape][i_s],
+ *   i_s = (c - s * a + floor(w / 2)) mod L,
+ * over the w / a windows s with i_s < w in ascending s; rescale counts every
+ * one of them, also those with all samples missing, which have no row and add
+ * zero to the first sum.  A table entry that does not name a row of window s,
+ * shape and L is taken as no row.  The value goes to signals[unit_off + j];
+ * observed samples are never written.
+ * history (nullable) [n_units][maxit][out_stride] from row_history
+ * [n_rows][maxit][hist_stride] (both or neither), the history the solver wrote
+ * for the rows (a caller with two solvers puts theirs side by side), where a
+ * row's history is in the order of its missing samples: position i_s -
+ * gap_start[r] for a row of one run, else the index of i_s in the row's list,
+ * found by a lower-bound search; a sample that is not among its row's missing
+ * samples adds nothing.  A NaN of row_history (an iteration a window did not
+ * complete, where the caller prefilled with NaN) goes through the sum.  No
+ * atomics, fixed order: the same bits on every call.  A unit whose entries
+ * contradict one another or reach outside `signals` or win_row is skipped.
  * Supported: a divides w, w / a >= 2, 2 <= w <= min(stride, 16384), n_shapes
- * >= 1, total >= 1; ola also 1 <= h_max <= 2048 (the longest h, sizes the
- * grid) and with history 1 <= maxit <= 1000, out_stride >= h_max.  Anything
- * else is AINP_EINVAL without a launch.  Neither needs a workspace. */
-int ainp_janssen_windows(const double* signals, int64_t total, const int64_t* sig_off,
-                         const int32_t* row_tab, const int32_t* gap_start,
-                         const int32_t* gap_len, int64_t n_rows, int w, int a,
-                         const double* gana, int n_shapes, double* sol, int64_t stride,
+ * >= 1, total >= 1; ola also 1 <= h_max <= total (the longest h, sizes the
+ * grid: at most 65535 * 256) and with history 1 <= maxit <= 1000, hist_stride
+ * >= 1, out_stride >= h_max.  Anything else is AINP_EINVAL without a launch.
+ * Neither needs a workspace. */
+int ainp_janssen_windows(const double* signals, const uint8_t* missing, int64_t total,
+                         const int64_t* sig_off, const int32_t* row_tab, int64_t n_rows, int w,
+                         int a, const double* gana, int n_shapes, double* sol, int64_t stride,
                          void* stream);
 int ainp_janssen_ola(const double* sol, int64_t n_rows, int64_t stride,
                      const double* row_history, int maxit, int64_t hist_stride,
                      const int32_t* row_tab, const int32_t* gap_start, const int32_t* gap_len,
-                     const int64_t* gap_off, const int32_t* gap_tab, int64_t n_gaps, int h_max,
-                     int w, int a, const double* gana, const double* gsyn, int n_shapes,
-                     double* signals, int64_t total, double* history, int64_t out_stride,
-                     void* stream);
-
-/* The same two streams for any mask (utils/segmentation_inp.m called on a whole
- * signal with any NaN pattern; ainp.janssen.janssen_windowed_mask).  The support
- * is the signal from its first sample, zero-padded (observed zeros) to the
- * circular length L = ceil(sig_len / a) * a + (w / a - 1) * a; the S = L / a
- * windows are those above and do not depend on the mask.  A row is a window
- * with some, not all, samples missing, in any number of runs: rows of one run
- * in window order are solved by ainp_janssen_ex, the others by
- * ainp_janssen_mask, both with n = w.
- *
- * ainp_janssen_windows_mask cuts the rows: sol[r][i] = signal sample *
- * gana[shape][i], zero where missing[] is non-zero and on the padding.
- * signals, sig_off, gana, sol, stride as above; missing: `total` bytes laid
- * out like signals, non-zero on a missing sample.  row_tab int32 [n_rows][4]:
- * sig_len, L, window index, shape.  A row whose entries contradict one another
- * (L < w, sig_len > L, window index * a >= L, shape >= n_shapes, a signal
- * outside [0, total)) is written as zeros.
- *
- * ainp_janssen_ola_mask puts the runs of missing samples back, one lane per
- * missing sample.  run_off int64 [n_runs]: the run's first sample in
- * `signals`; run_tab int32 [n_runs][5]: h (its samples; not limited to 2048),
- * c0 (signal index of the first), L, tab0, shape.  win_row int32 [n_tab]:
- * win_row[tab0 + s] is the row of window s of the run's (shape, signal), -1
- * for a window without a row -- with the wrap of the last windows to the head
- * of the signal a run's rows are not consecutive.  Per missing sample c = c0 + j
- *   value = sum_s sol[win_row[tab0 + s]][i_s] * gsyn[shape][i_s] / rescale,
- *   rescale = sum_s gana[shape][i_s] * gsyn[shape][i_s],
- *   i_s = (c - s * a + floor(w / 2)) mod L,
- * over the w / a windows s with i_s < w in ascending s; windows without a row
- * add zero to the first sum.  A table entry that does not name a row of window
- * s, shape and L is taken as no row.  The value goes to signals[run_off + j];
- * observed samples are never written.
- * history (nullable) [n_runs][maxit][out_stride] from row_history
- * [n_rows][maxit][hist_stride] (both or neither), where a row's history is in
- * the order of its missing list: position i_s - gap_start[r] for a row of one
- * run (gap_len[r] >= 1), else (gap_len[r] == 0) the index of i_s in the row's
- * strictly ascending list miss_idx[miss_off[r] .. miss_off[r + 1]) (miss_off
- * int32 [n_rows + 1], miss_idx int32 [n_idx], n_idx >= 1), found by a
- * lower-bound search; a sample that is not in its row's list adds nothing.  A
- * NaN of row_history goes through the sum.  No atomics, fixed order: the same
- * bits on every call.  A run whose entries contradict one another or reach
- * outside `signals` or win_row is skipped.
- * Supported: as above for w, a, stride, n_shapes, total; ola also 1 <= h_max
- * <= total (the longest h, sizes the grid: at most 65535 * 256) and with
- * history 1 <= maxit <= 1000, hist_stride >= 1, out_stride >= h_max.  Anything
- * else is AINP_EINVAL without a launch.  Neither needs a workspace. */
-int ainp_janssen_windows_mask(const double* signals, const uint8_t* missing, int64_t total,
-                              const int64_t* sig_off, const int32_t* row_tab, int64_t n_rows,
-                              int w, int a, const double* gana, int n_shapes, double* sol,
-                              int64_t stride, void* stream);
-int ainp_janssen_ola_mask(const double* sol, int64_t n_rows, int64_t stride,
-                          const double* row_history, int maxit, int64_t hist_stride,
-                          const int32_t* row_tab, const int32_t* gap_start,
-                          const int32_t* gap_len, const int32_t* miss_off,
-                          const int32_t* miss_idx, int64_t n_idx, const int32_t* win_row,
-                          int64_t n_tab, const int64_t* run_off, const int32_t* run_tab,
-                          int64_t n_runs, int64_t h_max, int w, int a, const double* gana,
-                          const double* gsyn, int n_shapes, double* signals, int64_t total,
-                          double* history, int64_t out_stride, void* stream);
+                     const int32_t* miss_off, const int32_t* miss_idx, int64_t n_idx,
+                     const int32_t* win_row, int64_t n_tab, const int64_t* unit_off,
+                     const int32_t* unit_tab, int64_t n_units, int64_t h_max, int w, int a,
+                     const double* gana, const double* gsyn, int n_shapes, double* signals,
+                     int64_t total, double* history, int64_t out_stride, void* stream);
 
 /* The two SPAIN algorithms (references/spain/aspain.m and sspain.m with
  * f_update = 'H'): the analysis and the synthesis variant of sparse audio

@@ -298,17 +298,12 @@ _SIGS = {
     "ainp_ar_extrapolate": (c_int, [P, c_int64, c_int64, P, P, P, c_int, c_int, c_int, P, P,
                                     c_size_t, P]),
     "ainp_ar_extrapolate_workspace": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
-    # window-wise Janssen: the gather and the overlap-add (csrc/janssen_windows.hip)
-    "ainp_janssen_windows": (c_int, [P, c_int64, P, P, P, P, c_int64, c_int, c_int, P, c_int, P,
+    # window-wise inpainting: the gather and the overlap-add (csrc/janssen_windows.hip)
+    "ainp_janssen_windows": (c_int, [P, P, c_int64, P, P, c_int64, c_int, c_int, P, c_int, P,
                                      c_int64, P]),
     "ainp_janssen_ola": (c_int, [P, c_int64, c_int64, P, c_int, c_int64, P, P, P, P, P, c_int64,
-                                 c_int, c_int, c_int, P, P, c_int, P, c_int64, P, c_int64, P]),
-    # the same for any mask, rows found through a window-to-row table
-    "ainp_janssen_windows_mask": (c_int, [P, P, c_int64, P, P, c_int64, c_int, c_int, P, c_int,
-                                          P, c_int64, P]),
-    "ainp_janssen_ola_mask": (c_int, [P, c_int64, c_int64, P, c_int, c_int64, P, P, P, P, P,
-                                      c_int64, P, c_int64, P, P, c_int64, c_int64, c_int, c_int,
-                                      P, P, c_int, P, c_int64, P, c_int64, P]),
+                                 P, c_int64, P, P, c_int64, c_int64, c_int, c_int, P, P, c_int,
+                                 P, c_int64, P, c_int64, P]),
     # A-SPAIN / S-SPAIN on a batch of windows (csrc/spain.hip)
     "ainp_spain": (c_int, [P, c_int64, c_int64, P, P, c_int, c_int, c_int, c_int, c_int, c_double,
                            c_int, P, P, P, c_size_t, P]),

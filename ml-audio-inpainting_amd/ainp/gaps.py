@@ -1,12 +1,14 @@
 """What the host sides of the audio-regression algorithms share (ainp/janssen.py,
 ainp/spain.py): the input layouts and the gap SDR, the windows of
 utils/segmentation_inp.m, and the window-wise batch -- the rows a gap makes on
-a circular support (window_rows), the tables of csrc/janssen_windows.hip
-(window_plan) and the three launches around a solver (solve_windows); and the
-same for whole signals with any mask (MaskWindowPlan, mask_window_plan,
-solve_windows_mask).
+a circular support (window_rows), the plan of a call with one support per gap
+(WindowPlan, window_plan) and of one on whole signals with any mask
+(MaskWindowPlan, mask_window_plan), the device tables of
+csrc/janssen_windows.hip that either gives (WindowTables, tables()) and the
+launches around the solvers (solve_windows).
 """
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -149,6 +151,21 @@ def window_pairs(keys, w, a, name_shape=True):
     return pairs
 
 
+class WindowTables(NamedTuple):
+    """The device tables of the gather and the overlap-add (include/ainp.h), as
+    host arrays: what ops.janssen_windows and ops.janssen_ola take."""
+    missing: np.ndarray       # uint8 [total], 1 on a missing sample
+    sig_off: np.ndarray       # int64 [n_rows]
+    row_tab: np.ndarray       # int32 [n_rows, 6]: sig_len, origin, sup_len, L, window, shape
+    gap_start: np.ndarray     # int32 [n_rows], relative to the window
+    gap_len: np.ndarray       # int32 [n_rows]: >= 1 a row of one run, 0 a row with a list
+    miss_off: np.ndarray      # int32 [n_rows + 1]
+    miss_idx: np.ndarray      # int32, window positions, ascending per row
+    win_row: np.ndarray       # int32: per support and shape the row of each window, -1: none
+    unit_off: np.ndarray      # int64 [n_units]
+    unit_tab: np.ndarray      # int32 [n_units, 5]: h, c0, L, tab0, shape
+
+
 @dataclass
 class WindowPlan:
     """The tables of one window-wise call.  Signals lie end to end in one
@@ -172,6 +189,22 @@ class WindowPlan:
 
     def __len__(self):
         return len(self.sig_off)
+
+    def tables(self):
+        """Every gap is a unit with a support of its own: its window-to-row
+        table is one segment of L / a entries, its rows have one run each."""
+        h, c0, L, row0, n_rows, shape = self.gap_tab.T.astype(np.int64)
+        tab0 = np.concatenate(([0], np.cumsum(L // self.a)))
+        missing = np.zeros(self.total, np.uint8)
+        win_row = np.full(int(tab0[-1]), -1, np.int32)
+        for g in range(len(h)):
+            missing[self.gap_off[g]:self.gap_off[g] + h[g]] = 1
+            rows = np.arange(row0[g], row0[g] + n_rows[g])
+            win_row[tab0[g] + self.row_tab[rows, 4]] = rows
+        unit_tab = np.stack((h, c0, L, tab0[:-1], shape), axis=1).astype(np.int32)
+        return WindowTables(missing, self.sig_off, self.row_tab, self.gap_start, self.gap_len,
+                            np.zeros(len(self) + 1, np.int32), np.zeros(0, np.int32), win_row,
+                            self.gap_off, unit_tab)
 
 
 def window_rows(miss_any, c0, w, a, windows, i, g0, g1):
@@ -229,26 +262,38 @@ def window_plan(keys, w, a, pairs, masks, gaps):
                       i32(gap_signal), i32(gap_range, 2))
 
 
-def solve_windows(sigs, plan, device, per_gap, solve):
-    """The three launches of a window-wise call: the signals, end to end once
-    per shape, go to the device; ops.janssen_windows gathers the rows;
-    solve(sol) -> (iters, history or None) solves them in place;
-    ops.janssen_ola adds them back (per_gap: and turns the rows' history into
-    the gaps').  -> (per shape the per-signal results, iters, history) as numpy.
-    An empty plan launches nothing: iters is empty, the history None."""
+def solve_windows(sigs, plan, device, parts, per_gap=True):
+    """The launches of a window-wise call: the signals, end to end once per
+    shape, and their byte mask go to the device; ops.janssen_windows gathers
+    the rows; every (first, end, solve) of `parts` with rows in it runs
+    solve(sol[first:end]) -> (iters, history or None) in place, once;
+    ops.janssen_ola adds the rows back (per_gap: and turns their history into
+    the units', else the rows' own history comes back untouched).  -> (per shape
+    the per-signal results, iters per row, history) as numpy.  A plan without
+    rows launches nothing: its missing samples, if any, belong to windows that
+    are all missing and stay zero; iters is empty, the history None."""
     import torch
     from . import ops
     buf = np.concatenate([s for _ in plan.wtypes for s in sigs]) if sigs else np.zeros(0)
     iters, hist = np.zeros(0, np.int32), None
     if len(plan):
+        tables = plan.tables()
         dbuf = torch.from_numpy(buf).to(device)
-        sol = ops.janssen_windows(dbuf, plan.sig_off, plan.row_tab, plan.gap_start,
-                                  plan.gap_len, plan.w, plan.a, plan.gana)
-        iters, hist = solve(sol)
-        gaps = ops.janssen_ola(sol, hist if per_gap else None, plan.row_tab, plan.gap_start,
-                               plan.gap_len, plan.gap_off, plan.gap_tab, plan.a, plan.gana,
-                               plan.gsyn, dbuf)
-        hist = gaps if per_gap else hist
+        sol = ops.janssen_windows(dbuf, torch.from_numpy(tables.missing).to(device), tables,
+                                  plan.w, plan.a, plan.gana)
+        done = [solve(sol[first:end]) for first, end, solve in parts if end > first]
+        iters, hist = torch.cat([it for it, _ in done]), done[0][1]
+        if len(done) > 1 and hist is not None:
+            # the solvers' histories side by side, NaN beyond a row's list
+            hist = torch.full((len(plan), hist.shape[1], max(h.shape[2] for _, h in done)),
+                              float("nan"), device=sol.device, dtype=torch.float64)
+            at = 0
+            for _, h in done:
+                hist[at:at + h.shape[0], :, :h.shape[2]] = h
+                at += h.shape[0]
+        units = ops.janssen_ola(sol, hist if per_gap else None, tables, plan.a, plan.gana,
+                                plan.gsyn, dbuf)
+        hist = units if per_gap else hist
         buf, iters = dbuf.cpu().numpy(), iters.cpu().numpy()
         hist = hist.cpu().numpy() if hist is not None else None
     out, at = [], 0
@@ -263,10 +308,10 @@ def solve_windows(sigs, plan, device, per_gap, solve):
 # ---------------------------------------------------------------- any mask
 @dataclass
 class MaskWindowPlan:
-    """The tables of one window-wise call on whole signals with any mask
-    (ainp_janssen_windows_mask / ainp_janssen_ola_mask).  Signals lie end to end
-    in one buffer, once per window shape (shape-major); signal i is padded to
-    the circular length L_i and has S_i = L_i / a windows whatever its mask.
+    """The tables of one window-wise call on whole signals with any mask.
+    Signals lie end to end in one buffer, once per window shape (shape-major);
+    signal i is its own support (origin 0, sup_len its length), padded to the
+    circular length L_i, and has S_i = L_i / a windows whatever its mask.
     One row per window that holds some, not all, missing samples: first the
     rows whose missing samples are one run in window order (rows [0, n_one),
     gap_start / gap_len), then the rows with a list (gap_len 0, miss_off /
@@ -280,7 +325,7 @@ class MaskWindowPlan:
     gsyn: np.ndarray
     missing: np.ndarray       # uint8 [total], 1 on a missing sample
     sig_off: np.ndarray       # int64 [n_rows]
-    row_tab: np.ndarray       # int32 [n_rows, 4]: sig_len, L, window, shape
+    row_tab: np.ndarray       # int32 [n_rows, 6]: sig_len, origin 0, sup_len, L, window, shape
     n_one: int
     gap_start: np.ndarray     # int32 [n_rows], relative to the window
     gap_len: np.ndarray
@@ -298,6 +343,12 @@ class MaskWindowPlan:
         """The missing lists of the rows [n_one, n_rows)."""
         return [self.miss_idx[self.miss_off[r]:self.miss_off[r + 1]]
                 for r in range(self.n_one, len(self))]
+
+    def tables(self):
+        """Every run of missing samples of a signal is a unit."""
+        return WindowTables(self.missing, self.sig_off, self.row_tab, self.gap_start,
+                            self.gap_len, self.miss_off, self.miss_idx, self.win_row,
+                            self.run_off, self.run_tab)
 
 
 def mask_window_plan(keys, w, a, pairs, masks, rows):
@@ -336,56 +387,9 @@ def mask_window_plan(keys, w, a, pairs, masks, rows):
         np.stack([g for g, _ in pairs]), np.stack([g for _, g in pairs]),
         np.tile(missing.astype(np.uint8), len(keys)),
         np.array([k * per_shape + int(starts[i]) for k, i, _, _ in order], dtype=np.int64),
-        i32([(len(masks[i]), Ls[i], n, k) for k, i, n, _ in order], 4), len(one),
+        i32([(len(masks[i]), 0, len(masks[i]), Ls[i], n, k) for k, i, n, _ in order], 6),
+        len(one),
         i32([wh[0] for *_, wh in one] + [0] * len(many)),
         i32([len(wh) for *_, wh in one] + [0] * len(many)),
         miss_off, np.concatenate(lists) if lists else np.zeros(0, np.int32), win_row,
         np.array(run_off, dtype=np.int64), i32(run_tab, 5), i32(run_signal))
-
-
-def solve_windows_mask(sigs, plan, device, solve_runs, solve_lists):
-    """The launches of a window-wise call on whole signals: the signals, end to
-    end once per shape, and their byte mask go to the device;
-    ops.janssen_windows_mask gathers the rows; solve_runs(sol[:n_one]) and
-    solve_lists(sol[n_one:]) -> (iters, history or None) solve the two parts in
-    place, each at most once; ops.janssen_ola_mask adds them back and turns the
-    rows' history into the runs'.  -> (per shape the per-signal results, iters
-    per row, history per run or None) as numpy.  A plan without rows launches
-    nothing: its missing samples belong to windows that are all missing and
-    stay zero; the history is None."""
-    import torch
-    from . import ops
-    buf = np.concatenate([s for _ in plan.wtypes for s in sigs]) if sigs else np.zeros(0)
-    iters, hist = np.zeros(0, np.int32), None
-    if len(plan):
-        dbuf = torch.from_numpy(buf).to(device)
-        sol = ops.janssen_windows_mask(dbuf, torch.from_numpy(plan.missing).to(device),
-                                       plan.sig_off, plan.row_tab, plan.w, plan.a, plan.gana)
-        parts = []
-        if plan.n_one:
-            parts.append(solve_runs(sol[:plan.n_one]))
-        if plan.n_one < len(plan):
-            parts.append(solve_lists(sol[plan.n_one:]))
-        iters = torch.cat([it for it, _ in parts])
-        row_hist = None
-        if parts[0][1] is not None:
-            # the two solvers' histories side by side, NaN beyond a row's list
-            row_hist = torch.full((len(plan), parts[0][1].shape[1],
-                                   max(h.shape[2] for _, h in parts)), float("nan"),
-                                  device=sol.device, dtype=torch.float64)
-            at = 0
-            for _, h in parts:
-                row_hist[at:at + h.shape[0], :, :h.shape[2]] = h
-                at += h.shape[0]
-        hist = ops.janssen_ola_mask(sol, row_hist, plan.row_tab, plan.gap_start, plan.gap_len,
-                                    plan.miss_off, plan.miss_idx, plan.win_row, plan.run_off,
-                                    plan.run_tab, plan.a, plan.gana, plan.gsyn, dbuf)
-        buf, iters = dbuf.cpu().numpy(), iters.cpu().numpy()
-        hist = hist.cpu().numpy() if hist is not None else None
-    out, at = [], 0
-    for _ in plan.wtypes:
-        out.append([])
-        for s in sigs:
-            out[-1].append(buf[at:at + len(s)].copy())
-            at += len(s)
-    return out, iters, hist

@@ -19,8 +19,7 @@ ainp_janssen_ex launch, between the gather and the overlap-add of
 csrc/janssen_windows.hip.  plan_windows_mask / janssen_windowed_mask after them
 are segmentation_inp.m on a whole signal with any mask: one window grid per
 signal, windows with one run of missing samples to ainp_janssen_ex, the others
-to ainp_janssen_mask, between the any-mask gather and overlap-add of the same
-file.
+to ainp_janssen_mask, between the same gather and overlap-add.
 """
 from __future__ import annotations
 
@@ -30,8 +29,8 @@ import numpy as np
 
 from .gaps import (WTYPES, MaskWindowPlan, WindowPlan, _cdiv, _normalise,  # noqa: F401
                    _to_numpy, check_shift, find_gaps, gap_sdr, mask_window_plan, restack,
-                   solve_windows, solve_windows_mask, window_pair, window_pairs, window_plan,
-                   window_rescale, window_rows, wtype_key)
+                   solve_windows, window_pair, window_pairs, window_plan, window_rescale,
+                   window_rows, wtype_key)
 
 P_MAX = 3072          # csrc/ar_limits.h JN_PMAX
 N_MAX = 16384         # JN_NMAX
@@ -375,10 +374,10 @@ def janssen_windowed(signal, mask=None, p=512, w=4096, a=1024, wtype="hann", max
     plan = plan_windows(masks, p, w, a, shapes)
     keys = plan.wtypes
     res, iters, hist = solve_windows(
-        sigs, plan, device, per_gap=True,
-        solve=lambda sol: ops.janssen(sol, np.full(len(plan), plan.w), plan.gap_start,
-                                      plan.gap_len, p, maxit, return_history=return_history,
-                                      method=method))
+        sigs, plan, device,
+        [(0, len(plan), lambda sol: ops.janssen(sol, np.full(len(plan), plan.w), plan.gap_start,
+                                                plan.gap_len, p, maxit,
+                                                return_history=return_history, method=method))])
     info = {k: [] for k in keys}
     for g in range(len(plan.gap_off)):
         h, _, _, row0, nrows, k = (int(v) for v in plan.gap_tab[g])
@@ -467,13 +466,15 @@ def janssen_windowed_mask(signal, mask=None, p=512, w=4096, a=1024, wtype="hann"
     plan = plan_windows_mask(masks, p, w, a, shapes)
     keys = plan.wtypes
     full = lambda rows: np.full(rows, plan.w)
-    res, iters, hist = solve_windows_mask(
+    res, iters, hist = solve_windows(
         sigs, plan, device,
-        lambda sol: ops.janssen(sol, full(plan.n_one), plan.gap_start[:plan.n_one],
-                                plan.gap_len[:plan.n_one], p, maxit,
-                                return_history=return_history, method=method),
-        lambda sol: ops.janssen_mask(sol, full(len(plan) - plan.n_one), plan.lists(), p, maxit,
-                                     return_history=return_history, method=method))
+        [(0, plan.n_one,
+          lambda sol: ops.janssen(sol, full(plan.n_one), plan.gap_start[:plan.n_one],
+                                  plan.gap_len[:plan.n_one], p, maxit,
+                                  return_history=return_history, method=method)),
+         (plan.n_one, len(plan),
+          lambda sol: ops.janssen_mask(sol, full(len(plan) - plan.n_one), plan.lists(), p, maxit,
+                                       return_history=return_history, method=method))])
     info = {k: [] for k in keys}
     for g in range(len(plan.run_off)):
         h, c0, L, tab0, k = (int(v) for v in plan.run_tab[g])

@@ -2368,178 +2368,30 @@ def ar_extrapolate(sol, n, gap_start, gap_len, p, w, method="lpc"):
     return status
 
 
-def _window_tables(sol_rows, w, a, sig_off, row_tab, gap_start, gap_len, gana, total):
-    """The host checks the two window-wise launches share -> the tables as
-    numpy (int64 sig_off, int32 the rest).  sig_off None: the overlap-add, which
-    reads no signal through a row."""
+def _window_tables(t, nrows, w, a, n_shapes, total):
+    """The host checks of the tables of the two window-wise launches (`t`: what
+    a plan's tables() gives, include/ainp.h describes them) -> sig_off, row_tab,
+    gap_start, gap_len, miss_off, miss_idx, win_row, unit_off, unit_tab as numpy
+    (int64 the two offsets into the buffer, int32 the rest)."""
     w, a = int(w), int(a)
     if a < 1 or w % a or w // a < 2 or not 2 <= w <= _jn.W_MAX:
         raise ValueError(f"a must divide w, w / a >= 2 and 2 <= w <= {_jn.W_MAX}")
-    rt = np.ascontiguousarray(np.asarray(row_tab, dtype=np.int32).reshape(-1, 6))
-    gs = np.asarray(gap_start, dtype=np.int32).reshape(-1)
-    gl = np.asarray(gap_len, dtype=np.int32).reshape(-1)
-    so = None if sig_off is None else np.asarray(sig_off, dtype=np.int64).reshape(-1)
-    if not (len(rt) == len(gs) == len(gl) == sol_rows and (so is None or len(so) == sol_rows)):
-        raise ValueError("sig_off, row_tab, gap_start and gap_len need one entry per row")
-    if gana.ndim != 2 or gana.shape[1] != w:
-        raise ValueError("the windows must be [n_shapes, w]")
+    so = np.asarray(t.sig_off, dtype=np.int64).reshape(-1)
+    rt = np.ascontiguousarray(np.asarray(t.row_tab, dtype=np.int32).reshape(-1, 6))
+    gs = np.asarray(t.gap_start, dtype=np.int64).reshape(-1)
+    gl = np.asarray(t.gap_len, dtype=np.int64).reshape(-1)
+    mo = np.asarray(t.miss_off, dtype=np.int64).reshape(-1)
+    mi = np.asarray(t.miss_idx, dtype=np.int64).reshape(-1)
+    if not (len(so) == len(rt) == len(gs) == len(gl) == nrows and len(mo) == nrows + 1):
+        raise ValueError("sig_off, row_tab, gap_start and gap_len need one entry per row, "
+                         "miss_off one more")
     sig_len, _, sup_len, L, win, shape = rt.T.astype(np.int64)
-    if sol_rows and not (np.all(L >= w) and np.all(L % a == 0) and np.all(sup_len >= 0)
-                         and np.all(sup_len <= L) and np.all(win >= 0) and np.all(win * a < L)
-                         and np.all(shape >= 0) and np.all(shape < gana.shape[0])):
+    if not (np.all(L >= w) and np.all(L % a == 0) and np.all(sup_len >= 0)
+            and np.all(sup_len <= L) and np.all(win >= 0) and np.all(win * a < L)
+            and np.all(shape >= 0) and np.all(shape < n_shapes)):
         raise ValueError("row_tab describes a window outside its support")
-    if sol_rows and so is not None and not (np.all(sig_len >= 0) and np.all(so >= 0)
-                                            and np.all(so + sig_len <= total)):
+    if not (np.all(sig_len >= 0) and np.all(so >= 0) and np.all(so + sig_len <= total)):
         raise ValueError("row_tab describes a signal outside the buffer")
-    _check_runs(gs, gl, w, "run must lie inside its window")
-    return so, rt, gs, gl
-
-
-def janssen_windows(signals, sig_off, row_tab, gap_start, gap_len, w, a, gana):
-    """ainp_janssen_windows: cut the windows of the window-wise Janssen
-    algorithm out of their signals.  signals: flat float64 cuda buffer, every
-    signal end to end; the tables (host integers, checked here) and gana
-    [n_shapes, w] (host float64) as include/ainp.h describes them.  Returns sol
-    [n_rows, w] float64: signal * gana, zeros on the row's missing run, on the
-    padding and outside the signal."""
-    _req(signals, "signals", dtype=torch.float64)
-    if signals.dim() != 1 or signals.numel() < 1:
-        raise ValueError("signals must be one flat, non-empty buffer")
-    gana = np.ascontiguousarray(gana, dtype=np.float64)
-    nrows = len(np.asarray(sig_off).reshape(-1))
-    so, rt, gs, gl = _window_tables(nrows, w, a, sig_off, row_tab, gap_start, gap_len, gana,
-                                    signals.numel())
-    dv = signals.device
-    sol = torch.empty(nrows, int(w), device=dv, dtype=torch.float64)
-    if nrows:
-        _T.janssen_windows(signals, torch.from_numpy(so).to(dv), _dev_i32(rt, dv),
-                           _dev_i32(gs, dv), _dev_i32(gl, dv), int(a),
-                           torch.from_numpy(gana).to(dv), sol)
-    return sol
-
-
-def janssen_ola(sol, row_history, row_tab, gap_start, gap_len, gap_off, gap_tab, a, gana, gsyn,
-                signals):
-    """ainp_janssen_ola: overlap-add the solved windows `sol` [n_rows, w] back
-    into the gaps of `signals` (flat float64 cuda buffer, written on the
-    missing samples only) and divide by the window weight.  row_history: the
-    history ainp_janssen_ex wrote for the rows, or None; with it returns
-    history [n_gaps, maxit, max h] float64 (NaN beyond a gap's h), else None.
-    Tables as include/ainp.h describes them, host integers checked here."""
-    _req(sol, "sol", dtype=torch.float64)
-    _req(signals, "signals", dtype=torch.float64)
-    if sol.dim() != 2 or signals.dim() != 1 or signals.numel() < 1:
-        raise ValueError("sol must be [n_rows, w] and signals one flat, non-empty buffer")
-    nrows, w = sol.shape
-    total = signals.numel()
-    gana = np.ascontiguousarray(gana, dtype=np.float64)
-    gsyn = np.ascontiguousarray(gsyn, dtype=np.float64)
-    if gsyn.shape != gana.shape:
-        raise ValueError("gana and gsyn must have one shape")
-    _, rt, gs, gl = _window_tables(nrows, w, a, None, row_tab, gap_start, gap_len, gana, total)
-    go = np.asarray(gap_off, dtype=np.int64).reshape(-1)
-    gt = np.ascontiguousarray(np.asarray(gap_tab, dtype=np.int32).reshape(-1, 6))
-    if len(go) != len(gt):
-        raise ValueError("gap_off and gap_tab need one entry per gap")
-    ngaps = len(go)
-    h, c0, L, row0, nr, shape = gt.T.astype(np.int64)
-    if ngaps and not (np.all(h >= 1) and np.all(h <= _jn.GAP_MAX) and np.all(c0 >= 0)
-                      and np.all(c0 + h <= L) and np.all(L >= w) and np.all(L % int(a) == 0)
-                      and np.all(row0 >= 0) and np.all(nr >= 0) and np.all(row0 + nr <= nrows)
-                      and np.all(shape >= 0) and np.all(shape < gana.shape[0])
-                      and np.all(go >= 0) and np.all(go + h <= total)):
-        raise ValueError(f"gap_tab describes a gap outside its support, its rows or the buffer "
-                         f"(1 <= h <= {_jn.GAP_MAX})")
-    dv = sol.device
-    hist = None
-    if row_history is not None:
-        _req(row_history, "row_history", dtype=torch.float64)
-        if row_history.dim() != 3 or row_history.shape[0] != nrows:
-            raise ValueError("row_history must be [n_rows, maxit, max gap_len]")
-        hist = torch.full((ngaps, row_history.shape[1], int(h.max()) if ngaps else 0),
-                          float("nan"), device=dv, dtype=torch.float64)
-    if ngaps:
-        up = lambda t: torch.from_numpy(t).to(dv)
-        _T.janssen_ola(sol, row_history, _dev_i32(rt, dv), _dev_i32(gs, dv), _dev_i32(gl, dv),
-                       up(go), _dev_i32(gt, dv), int(h.max()), int(a), up(gana), up(gsyn),
-                       signals, hist)
-    return hist
-
-
-def _mask_row_table(nrows, w, a, row_tab, n_shapes):
-    """The host checks of the rows of the two any-mask launches -> row_tab as
-    int32 numpy [n_rows, 4]: sig_len, L, window, shape."""
-    w, a = int(w), int(a)
-    if a < 1 or w % a or w // a < 2 or not 2 <= w <= _jn.W_MAX:
-        raise ValueError(f"a must divide w, w / a >= 2 and 2 <= w <= {_jn.W_MAX}")
-    rt = np.ascontiguousarray(np.asarray(row_tab, dtype=np.int32).reshape(-1, 4))
-    if len(rt) != nrows:
-        raise ValueError("row_tab needs one entry per row")
-    sig_len, L, win, shape = rt.T.astype(np.int64)
-    if nrows and not (np.all(L >= w) and np.all(L % a == 0) and np.all(sig_len >= 0)
-                      and np.all(sig_len <= L) and np.all(win >= 0) and np.all(win * a < L)
-                      and np.all(shape >= 0) and np.all(shape < n_shapes)):
-        raise ValueError("row_tab describes a window outside its support")
-    return rt
-
-
-def janssen_windows_mask(signals, missing, sig_off, row_tab, w, a, gana):
-    """ainp_janssen_windows_mask: cut the windows of the window-wise Janssen
-    algorithm out of whole signals with any pattern of missing samples.
-    signals: flat float64 cuda buffer, every signal end to end; missing: uint8
-    cuda buffer laid out like it, non-zero on a missing sample; the tables (host
-    integers, checked here) and gana [n_shapes, w] (host float64) as
-    include/ainp.h describes them.  Returns sol [n_rows, w] float64: signal *
-    gana, zeros on the missing samples and on the padding."""
-    _req(signals, "signals", dtype=torch.float64)
-    _req(missing, "missing", dtype=torch.uint8)
-    if signals.dim() != 1 or signals.numel() < 1 or missing.shape != signals.shape:
-        raise ValueError("signals must be one flat, non-empty buffer and missing one byte per "
-                         "sample of it")
-    gana = np.ascontiguousarray(gana, dtype=np.float64)
-    if gana.ndim != 2 or gana.shape[1] != int(w):
-        raise ValueError("the windows must be [n_shapes, w]")
-    so = np.asarray(sig_off, dtype=np.int64).reshape(-1)
-    nrows = len(so)
-    rt = _mask_row_table(nrows, w, a, row_tab, gana.shape[0])
-    if nrows and not (np.all(so >= 0) and np.all(so + rt[:, 0] <= signals.numel())):
-        raise ValueError("row_tab describes a signal outside the buffer")
-    dv = signals.device
-    sol = torch.empty(nrows, int(w), device=dv, dtype=torch.float64)
-    if nrows:
-        _T.janssen_windows_mask(signals, missing, torch.from_numpy(so).to(dv), _dev_i32(rt, dv),
-                                int(a), torch.from_numpy(gana).to(dv), sol)
-    return sol
-
-
-def janssen_ola_mask(sol, row_history, row_tab, gap_start, gap_len, miss_off, miss_idx, win_row,
-                     run_off, run_tab, a, gana, gsyn, signals):
-    """ainp_janssen_ola_mask: overlap-add the solved windows `sol` [n_rows, w]
-    back into the runs of missing samples of `signals` (flat float64 cuda
-    buffer, written on the missing samples only) and divide by the window
-    weight; a run's rows are found through win_row.  row_history: the rows'
-    history [n_rows, maxit, longest list] in the order of their missing lists,
-    or None; with it returns history [n_runs, maxit, max h] float64 (NaN beyond
-    a run's h), else None.  Tables as include/ainp.h describes them, host
-    integers checked here: gap_len[r] >= 1 for a row of one run, 0 for a row
-    whose list is miss_idx[miss_off[r]:miss_off[r + 1]]."""
-    _req(sol, "sol", dtype=torch.float64)
-    _req(signals, "signals", dtype=torch.float64)
-    if sol.dim() != 2 or signals.dim() != 1 or signals.numel() < 1:
-        raise ValueError("sol must be [n_rows, w] and signals one flat, non-empty buffer")
-    nrows, w = sol.shape
-    total = signals.numel()
-    gana = np.ascontiguousarray(gana, dtype=np.float64)
-    gsyn = np.ascontiguousarray(gsyn, dtype=np.float64)
-    if gana.ndim != 2 or gana.shape[1] != w or gsyn.shape != gana.shape:
-        raise ValueError("gana and gsyn must both be [n_shapes, w]")
-    rt = _mask_row_table(nrows, w, a, row_tab, gana.shape[0])
-    gs = np.asarray(gap_start, dtype=np.int64).reshape(-1)
-    gl = np.asarray(gap_len, dtype=np.int64).reshape(-1)
-    mo = np.asarray(miss_off, dtype=np.int64).reshape(-1)
-    mi = np.asarray(miss_idx, dtype=np.int64).reshape(-1)
-    if not (len(gs) == len(gl) == nrows and len(mo) == nrows + 1):
-        raise ValueError("gap_start and gap_len need one entry per row, miss_off one more")
     cnt = np.diff(mo)
     if not (mo[0] >= 0 and np.all(cnt >= 0) and mo[-1] <= len(mi)):
         raise ValueError("miss_off must ascend from >= 0 to <= len(miss_idx)")
@@ -2553,36 +2405,82 @@ def janssen_ola_mask(sol, row_history, row_tab, gap_start, gap_len, miss_off, mi
         v = mi[mo[r]:mo[r + 1]]
         if not (v[0] >= 0 and v[-1] < w and np.all(np.diff(v) > 0)):
             raise ValueError(f"row {r}: the missing samples must ascend strictly inside [0, {w})")
-    wr = np.asarray(win_row, dtype=np.int64).reshape(-1)
+    wr = np.asarray(t.win_row, dtype=np.int64).reshape(-1)
     if not (np.all(wr >= -1) and np.all(wr < nrows)):
         raise ValueError("win_row names a row that does not exist")
-    ro = np.asarray(run_off, dtype=np.int64).reshape(-1)
-    ru = np.ascontiguousarray(np.asarray(run_tab, dtype=np.int32).reshape(-1, 5))
-    if len(ro) != len(ru):
-        raise ValueError("run_off and run_tab need one entry per run")
-    nruns = len(ro)
-    h, c0, L, tab0, shape = ru.T.astype(np.int64)
-    if nruns and not (np.all(h >= 1) and np.all(c0 >= 0) and np.all(c0 + h <= L)
-                      and np.all(L >= w) and np.all(L % int(a) == 0) and np.all(tab0 >= 0)
-                      and np.all(tab0 + L // int(a) <= len(wr)) and np.all(shape >= 0)
-                      and np.all(shape < gana.shape[0]) and np.all(ro >= 0)
-                      and np.all(ro + h <= total)):
-        raise ValueError("run_tab describes a run outside its support, win_row or the buffer")
+    uo = np.asarray(t.unit_off, dtype=np.int64).reshape(-1)
+    ut = np.ascontiguousarray(np.asarray(t.unit_tab, dtype=np.int32).reshape(-1, 5))
+    if len(uo) != len(ut):
+        raise ValueError("unit_off and unit_tab need one entry per unit")
+    h, c0, L, tab0, shape = ut.T.astype(np.int64)
+    if not (np.all(h >= 1) and np.all(c0 >= 0) and np.all(c0 + h <= L) and np.all(L >= w)
+            and np.all(L % a == 0) and np.all(tab0 >= 0) and np.all(tab0 + L // a <= len(wr))
+            and np.all(shape >= 0) and np.all(shape < n_shapes) and np.all(uo >= 0)
+            and np.all(uo + h <= total)):
+        raise ValueError("unit_tab describes a run outside its support, win_row or the buffer")
+    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)
+    return so, rt, i32(gs), i32(gl), i32(mo), i32(mi if len(mi) else np.zeros(1)), i32(wr), uo, ut
+
+
+def janssen_windows(signals, missing, tables, w, a, gana):
+    """ainp_janssen_windows: cut the windows of a window-wise algorithm out of
+    their signals.  signals: flat float64 cuda buffer, every signal end to end;
+    missing: uint8 cuda buffer laid out like it, non-zero on a missing sample;
+    tables: what a plan's tables() gives (host integers, all of them checked
+    here) and gana [n_shapes, w] (host float64) as include/ainp.h describes
+    them.  Returns sol [n_rows, w] float64: signal * gana, zeros on the missing
+    samples, on the padding and outside the signal."""
+    _req(signals, "signals", dtype=torch.float64)
+    _req(missing, "missing", dtype=torch.uint8)
+    if signals.dim() != 1 or signals.numel() < 1 or missing.shape != signals.shape:
+        raise ValueError("signals must be one flat, non-empty buffer and missing one byte per "
+                         "sample of it")
+    gana = np.ascontiguousarray(gana, dtype=np.float64)
+    if gana.ndim != 2 or gana.shape[1] != int(w):
+        raise ValueError("the windows must be [n_shapes, w]")
+    nrows = len(np.asarray(tables.sig_off).reshape(-1))
+    so, rt = _window_tables(tables, nrows, w, a, gana.shape[0], signals.numel())[:2]
+    dv = signals.device
+    sol = torch.empty(nrows, int(w), device=dv, dtype=torch.float64)
+    if nrows:
+        _T.janssen_windows(signals, missing, torch.from_numpy(so).to(dv), _dev_i32(rt, dv),
+                           int(a), torch.from_numpy(gana).to(dv), sol)
+    return sol
+
+
+def janssen_ola(sol, row_history, tables, a, gana, gsyn, signals):
+    """ainp_janssen_ola: overlap-add the solved windows `sol` [n_rows, w] back
+    into the units (runs of missing samples) of `signals` (flat float64 cuda
+    buffer, written on the missing samples only) and divide by the window
+    weight; a unit's rows are found through win_row.  row_history: the rows'
+    history [n_rows, maxit, longest list] in the order of their missing
+    samples, or None; with it returns history [n_units, maxit, max h] float64
+    (NaN beyond a unit's h), else None.  tables: what a plan's tables() gives,
+    host integers checked here."""
+    _req(sol, "sol", dtype=torch.float64)
+    _req(signals, "signals", dtype=torch.float64)
+    if sol.dim() != 2 or signals.dim() != 1 or signals.numel() < 1:
+        raise ValueError("sol must be [n_rows, w] and signals one flat, non-empty buffer")
+    nrows, w = sol.shape
+    gana = np.ascontiguousarray(gana, dtype=np.float64)
+    gsyn = np.ascontiguousarray(gsyn, dtype=np.float64)
+    if gana.ndim != 2 or gana.shape[1] != w or gsyn.shape != gana.shape:
+        raise ValueError("gana and gsyn must both be [n_shapes, w]")
+    _, rt, gs, gl, mo, mi, wr, uo, ut = _window_tables(tables, nrows, w, a, gana.shape[0],
+                                                       signals.numel())
+    nunits, h_max = len(uo), int(ut[:, 0].max(initial=0))
     dv = sol.device
     hist = None
     if row_history is not None:
         _req(row_history, "row_history", dtype=torch.float64)
         if row_history.dim() != 3 or row_history.shape[0] != nrows:
             raise ValueError("row_history must be [n_rows, maxit, longest list]")
-        hist = torch.full((nruns, row_history.shape[1], int(h.max()) if nruns else 0),
-                          float("nan"), device=dv, dtype=torch.float64)
-    if nruns:
+        hist = torch.full((nunits, row_history.shape[1], h_max), float("nan"), device=dv,
+                          dtype=torch.float64)
+    if nunits:
         up = lambda t: torch.from_numpy(t).to(dv)
-        _T.janssen_ola_mask(sol, row_history, _dev_i32(rt, dv), _dev_i32(gs, dv),
-                            _dev_i32(gl, dv), _dev_i32(mo, dv),
-                            _dev_i32(mi if len(mi) else np.zeros(1), dv), _dev_i32(wr, dv),
-                            up(ro), _dev_i32(ru, dv), int(h.max()), int(a), up(gana), up(gsyn),
-                            signals, hist)
+        _T.janssen_ola(sol, row_history, up(rt), up(gs), up(gl), up(mo), up(mi), up(wr), up(uo),
+                       up(ut), h_max, int(a), up(gana), up(gsyn), signals, hist)
     return hist
 
 

@@ -8,7 +8,8 @@ of w samples every a samples and runs SPAIN on every window with missing
 samples.  Here every such window, of every gap and signal, is one row of one
 ainp_spain launch (csrc/spain.hip, float64; ainp_spain_omp of
 csrc/spain_omp.hip with f_update "OMP") between the gather and the
-overlap-add of csrc/janssen_windows.hip, which take this layout as it is.
+overlap-add of csrc/janssen_windows.hip, whose tables the plan gives
+(WindowPlan.tables: the signal is its own support, every gap a unit).
 """
 from __future__ import annotations
 
@@ -172,7 +173,7 @@ def _spain_inpaint(signal, mask, algorithm, w, a, wtype, red, s, r, epsilon, max
         atoms.append(na)
         return it, hist
 
-    (res,), iters, obj = solve_windows(sigs, plan, device, per_gap=False, solve=solve)
+    (res,), iters, obj = solve_windows(sigs, plan, device, [(0, len(plan), solve)], per_gap=False)
     if obj is None and return_history:
         obj = np.zeros((0, maxit))           # an empty plan
     atoms = (atoms[0].cpu().numpy() if atoms and atoms[0] is not None

@@ -490,87 +490,9 @@ void ar_extrapolate(const Tensor& sol, const Tensor& n, const Tensor& gap_start,
       "ar_extrapolate");
 }
 
-// window-wise Janssen: the gather into the batch and the overlap-add out of it
-void janssen_windows(const Tensor& signals, const Tensor& sig_off, const Tensor& row_tab,
-                     const Tensor& gap_start, const Tensor& gap_len, int64_t a,
-                     const Tensor& gana, const Tensor& sol) {
-  GUARD(sol);
-  TORCH_CHECK(sol.dim() == 2, "sol must be [n_rows, w]");
-  TORCH_CHECK(gana.dim() == 2 && gana.size(1) == sol.size(1), "gana must be [n_shapes, w]");
-  TORCH_CHECK(signals.dim() == 1, "signals must be one flat buffer");
-  const int64_t n_rows = sol.size(0), w = sol.size(1);
-  TORCH_CHECK(a >= 1 && a <= INT32_MAX && w <= INT32_MAX && gana.size(0) <= INT32_MAX,
-              "a must be positive");
-  numel_is(sig_off, n_rows, "sig_off");
-  numel_is(row_tab, n_rows * 6, "row_tab");
-  numel_is(gap_start, n_rows, "gap_start");
-  numel_is(gap_len, n_rows, "gap_len");
-  for (const Tensor* t : {&signals, &sig_off, &row_tab, &gap_start, &gap_len, &gana})
-    same_device(sol, *t);
-  chk(ainp_janssen_windows(dev<double>(signals, "signals", at::kDouble), signals.numel(),
-                           dev<int64_t>(sig_off, "sig_off", at::kLong),
-                           dev<int32_t>(row_tab, "row_tab", at::kInt),
-                           dev<int32_t>(gap_start, "gap_start", at::kInt),
-                           dev<int32_t>(gap_len, "gap_len", at::kInt), n_rows, (int)w, (int)a,
-                           dev<double>(gana, "gana", at::kDouble), (int)gana.size(0),
-                           dev<double>(sol, "sol", at::kDouble), w, stream_of(sol)),
-      "janssen_windows");
-}
-
-void janssen_ola(const Tensor& sol, const OptT& row_history, const Tensor& row_tab,
-                 const Tensor& gap_start, const Tensor& gap_len, const Tensor& gap_off,
-                 const Tensor& gap_tab, int64_t h_max, int64_t a, const Tensor& gana,
-                 const Tensor& gsyn, const Tensor& signals, const OptT& history) {
-  GUARD(sol);
-  TORCH_CHECK(sol.dim() == 2, "sol must be [n_rows, w]");
-  TORCH_CHECK(gana.dim() == 2 && gana.size(1) == sol.size(1), "gana must be [n_shapes, w]");
-  TORCH_CHECK(gsyn.sizes() == gana.sizes(), "gsyn must be [n_shapes, w] as gana");
-  TORCH_CHECK(signals.dim() == 1, "signals must be one flat buffer");
-  const int64_t n_rows = sol.size(0), w = sol.size(1), n_gaps = gap_off.numel();
-  TORCH_CHECK(a >= 1 && a <= INT32_MAX && w <= INT32_MAX && gana.size(0) <= INT32_MAX &&
-                  h_max >= 1 && h_max <= INT32_MAX,
-              "a and h_max must be positive");
-  numel_is(row_tab, n_rows * 6, "row_tab");
-  numel_is(gap_start, n_rows, "gap_start");
-  numel_is(gap_len, n_rows, "gap_len");
-  numel_is(gap_tab, n_gaps * 6, "gap_tab");
-  for (const Tensor* t : {&row_tab, &gap_start, &gap_len, &gap_off, &gap_tab, &gana, &gsyn,
-                          &signals})
-    same_device(sol, *t);
-  const double* rh = opt<double>(row_history, "row_history", at::kDouble);
-  double* h = opt<double>(history, "history", at::kDouble);
-  TORCH_CHECK((rh != nullptr) == (h != nullptr), "history needs row_history and the reverse");
-  int64_t maxit = 0, hist_stride = 0, out_stride = 0;
-  if (h) {
-    same_device(sol, *row_history);
-    same_device(sol, *history);
-    TORCH_CHECK(row_history->dim() == 3 && row_history->size(0) == n_rows,
-                "row_history must be [n_rows, maxit, max gap_len], got ", row_history->sizes());
-    maxit = row_history->size(1);
-    hist_stride = row_history->size(2);
-    TORCH_CHECK(history->dim() == 3 && history->size(0) == n_gaps &&
-                    history->size(1) == maxit && history->size(2) >= h_max,
-                "history must be [n_gaps, maxit, >= h_max], got ", history->sizes());
-    TORCH_CHECK(maxit <= INT32_MAX, "maxit too large");
-    out_stride = history->size(2);
-  }
-  chk(ainp_janssen_ola(dev<double>(sol, "sol", at::kDouble), n_rows, w, rh, (int)maxit,
-                       hist_stride, dev<int32_t>(row_tab, "row_tab", at::kInt),
-                       dev<int32_t>(gap_start, "gap_start", at::kInt),
-                       dev<int32_t>(gap_len, "gap_len", at::kInt),
-                       dev<int64_t>(gap_off, "gap_off", at::kLong),
-                       dev<int32_t>(gap_tab, "gap_tab", at::kInt), n_gaps, (int)h_max, (int)w,
-                       (int)a, dev<double>(gana, "gana", at::kDouble),
-                       dev<double>(gsyn, "gsyn", at::kDouble), (int)gana.size(0),
-                       dev<double>(signals, "signals", at::kDouble), signals.numel(), h,
-                       out_stride, stream_of(sol)),
-      "janssen_ola");
-}
-
-// the same for any mask: rows found through the window-to-row table win_row
-void janssen_windows_mask(const Tensor& signals, const Tensor& missing, const Tensor& sig_off,
-                          const Tensor& row_tab, int64_t a, const Tensor& gana,
-                          const Tensor& sol) {
+// window-wise inpainting: the gather into the batch and the overlap-add out of it
+void janssen_windows(const Tensor& signals, const Tensor& missing, const Tensor& sig_off,
+                     const Tensor& row_tab, int64_t a, const Tensor& gana, const Tensor& sol) {
   GUARD(sol);
   TORCH_CHECK(sol.dim() == 2, "sol must be [n_rows, w]");
   TORCH_CHECK(gana.dim() == 2 && gana.size(1) == sol.size(1), "gana must be [n_shapes, w]");
@@ -580,39 +502,38 @@ void janssen_windows_mask(const Tensor& signals, const Tensor& missing, const Te
               "a must be positive");
   numel_is(missing, signals.numel(), "missing");
   numel_is(sig_off, n_rows, "sig_off");
-  numel_is(row_tab, n_rows * 4, "row_tab");
+  numel_is(row_tab, n_rows * 6, "row_tab");
   for (const Tensor* t : {&signals, &missing, &sig_off, &row_tab, &gana}) same_device(sol, *t);
-  chk(ainp_janssen_windows_mask(dev<double>(signals, "signals", at::kDouble),
-                                dev<uint8_t>(missing, "missing", at::kByte), signals.numel(),
-                                dev<int64_t>(sig_off, "sig_off", at::kLong),
-                                dev<int32_t>(row_tab, "row_tab", at::kInt), n_rows, (int)w,
-                                (int)a, dev<double>(gana, "gana", at::kDouble),
-                                (int)gana.size(0), dev<double>(sol, "sol", at::kDouble), w,
-                                stream_of(sol)),
-      "janssen_windows_mask");
+  chk(ainp_janssen_windows(dev<double>(signals, "signals", at::kDouble),
+                           dev<uint8_t>(missing, "missing", at::kByte), signals.numel(),
+                           dev<int64_t>(sig_off, "sig_off", at::kLong),
+                           dev<int32_t>(row_tab, "row_tab", at::kInt), n_rows, (int)w, (int)a,
+                           dev<double>(gana, "gana", at::kDouble), (int)gana.size(0),
+                           dev<double>(sol, "sol", at::kDouble), w, stream_of(sol)),
+      "janssen_windows");
 }
 
-void janssen_ola_mask(const Tensor& sol, const OptT& row_history, const Tensor& row_tab,
-                      const Tensor& gap_start, const Tensor& gap_len, const Tensor& miss_off,
-                      const Tensor& miss_idx, const Tensor& win_row, const Tensor& run_off,
-                      const Tensor& run_tab, int64_t h_max, int64_t a, const Tensor& gana,
-                      const Tensor& gsyn, const Tensor& signals, const OptT& history) {
+void janssen_ola(const Tensor& sol, const OptT& row_history, const Tensor& row_tab,
+                 const Tensor& gap_start, const Tensor& gap_len, const Tensor& miss_off,
+                 const Tensor& miss_idx, const Tensor& win_row, const Tensor& unit_off,
+                 const Tensor& unit_tab, int64_t h_max, int64_t a, const Tensor& gana,
+                 const Tensor& gsyn, const Tensor& signals, const OptT& history) {
   GUARD(sol);
   TORCH_CHECK(sol.dim() == 2, "sol must be [n_rows, w]");
   TORCH_CHECK(gana.dim() == 2 && gana.size(1) == sol.size(1), "gana must be [n_shapes, w]");
   TORCH_CHECK(gsyn.sizes() == gana.sizes(), "gsyn must be [n_shapes, w] as gana");
   TORCH_CHECK(signals.dim() == 1, "signals must be one flat buffer");
-  const int64_t n_rows = sol.size(0), w = sol.size(1), n_runs = run_off.numel();
+  const int64_t n_rows = sol.size(0), w = sol.size(1), n_units = unit_off.numel();
   TORCH_CHECK(a >= 1 && a <= INT32_MAX && w <= INT32_MAX && gana.size(0) <= INT32_MAX &&
                   h_max >= 1,
               "a and h_max must be positive");
-  numel_is(row_tab, n_rows * 4, "row_tab");
+  numel_is(row_tab, n_rows * 6, "row_tab");
   numel_is(gap_start, n_rows, "gap_start");
   numel_is(gap_len, n_rows, "gap_len");
   numel_is(miss_off, n_rows + 1, "miss_off");
-  numel_is(run_tab, n_runs * 5, "run_tab");
+  numel_is(unit_tab, n_units * 5, "unit_tab");
   for (const Tensor* t : {&row_tab, &gap_start, &gap_len, &miss_off, &miss_idx, &win_row,
-                          &run_off, &run_tab, &gana, &gsyn, &signals})
+                          &unit_off, &unit_tab, &gana, &gsyn, &signals})
     same_device(sol, *t);
   const double* rh = opt<double>(row_history, "row_history", at::kDouble);
   double* h = opt<double>(history, "history", at::kDouble);
@@ -625,28 +546,27 @@ void janssen_ola_mask(const Tensor& sol, const OptT& row_history, const Tensor& 
                 "row_history must be [n_rows, maxit, longest list], got ", row_history->sizes());
     maxit = row_history->size(1);
     hist_stride = row_history->size(2);
-    TORCH_CHECK(history->dim() == 3 && history->size(0) == n_runs &&
+    TORCH_CHECK(history->dim() == 3 && history->size(0) == n_units &&
                     history->size(1) == maxit && history->size(2) >= h_max,
-                "history must be [n_runs, maxit, >= h_max], got ", history->sizes());
+                "history must be [n_units, maxit, >= h_max], got ", history->sizes());
     TORCH_CHECK(maxit <= INT32_MAX, "maxit too large");
     out_stride = history->size(2);
   }
-  chk(ainp_janssen_ola_mask(dev<double>(sol, "sol", at::kDouble), n_rows, w, rh, (int)maxit,
-                            hist_stride, dev<int32_t>(row_tab, "row_tab", at::kInt),
-                            dev<int32_t>(gap_start, "gap_start", at::kInt),
-                            dev<int32_t>(gap_len, "gap_len", at::kInt),
-                            dev<int32_t>(miss_off, "miss_off", at::kInt),
-                            dev<int32_t>(miss_idx, "miss_idx", at::kInt), miss_idx.numel(),
-                            dev<int32_t>(win_row, "win_row", at::kInt), win_row.numel(),
-                            dev<int64_t>(run_off, "run_off", at::kLong),
-                            dev<int32_t>(run_tab, "run_tab", at::kInt), n_runs, h_max, (int)w,
-                            (int)a, dev<double>(gana, "gana", at::kDouble),
-                            dev<double>(gsyn, "gsyn", at::kDouble), (int)gana.size(0),
-                            dev<double>(signals, "signals", at::kDouble), signals.numel(), h,
-                            out_stride, stream_of(sol)),
-      "janssen_ola_mask");
+  chk(ainp_janssen_ola(dev<double>(sol, "sol", at::kDouble), n_rows, w, rh, (int)maxit,
+                       hist_stride, dev<int32_t>(row_tab, "row_tab", at::kInt),
+                       dev<int32_t>(gap_start, "gap_start", at::kInt),
+                       dev<int32_t>(gap_len, "gap_len", at::kInt),
+                       dev<int32_t>(miss_off, "miss_off", at::kInt),
+                       dev<int32_t>(miss_idx, "miss_idx", at::kInt), miss_idx.numel(),
+                       dev<int32_t>(win_row, "win_row", at::kInt), win_row.numel(),
+                       dev<int64_t>(unit_off, "unit_off", at::kLong),
+                       dev<int32_t>(unit_tab, "unit_tab", at::kInt), n_units, h_max, (int)w,
+                       (int)a, dev<double>(gana, "gana", at::kDouble),
+                       dev<double>(gsyn, "gsyn", at::kDouble), (int)gana.size(0),
+                       dev<double>(signals, "signals", at::kDouble), signals.numel(), h,
+                       out_stride, stream_of(sol)),
+      "janssen_ola");
 }
-
 // SPAIN on the rows janssen_windows cut
 void spain(const Tensor& sol, const Tensor& gap_start, const Tensor& gap_len, int64_t red,
            int64_t algorithm, int64_t s, int64_t r, double epsilon, int64_t maxit,
@@ -2439,16 +2359,11 @@ TORCH_LIBRARY(ainp, m) {
         "-> ()");
   m.def("ar_extrapolate(Tensor(a!) sol, Tensor n, Tensor gap_start, Tensor gap_len, int p, int w, "
         "int method, Tensor(b!) status, Tensor? workspace) -> ()");
-  m.def("janssen_windows(Tensor signals, Tensor sig_off, Tensor row_tab, Tensor gap_start, "
-        "Tensor gap_len, int a, Tensor gana, Tensor(a!) sol) -> ()");
+  m.def("janssen_windows(Tensor signals, Tensor missing, Tensor sig_off, Tensor row_tab, int a, "
+        "Tensor gana, Tensor(a!) sol) -> ()");
   m.def("janssen_ola(Tensor sol, Tensor? row_history, Tensor row_tab, Tensor gap_start, "
-        "Tensor gap_len, Tensor gap_off, Tensor gap_tab, int h_max, int a, Tensor gana, "
-        "Tensor gsyn, Tensor(a!) signals, Tensor(b!)? history) -> ()");
-  m.def("janssen_windows_mask(Tensor signals, Tensor missing, Tensor sig_off, Tensor row_tab, "
-        "int a, Tensor gana, Tensor(a!) sol) -> ()");
-  m.def("janssen_ola_mask(Tensor sol, Tensor? row_history, Tensor row_tab, Tensor gap_start, "
-        "Tensor gap_len, Tensor miss_off, Tensor miss_idx, Tensor win_row, Tensor run_off, "
-        "Tensor run_tab, int h_max, int a, Tensor gana, Tensor gsyn, Tensor(a!) signals, "
+        "Tensor gap_len, Tensor miss_off, Tensor miss_idx, Tensor win_row, Tensor unit_off, "
+        "Tensor unit_tab, int h_max, int a, Tensor gana, Tensor gsyn, Tensor(a!) signals, "
         "Tensor(b!)? history) -> ()");
   m.def("spain(Tensor(a!) sol, Tensor gap_start, Tensor gap_len, int red, int algorithm, int s, "
         "int r, float epsilon, int maxit, Tensor(b!) iters, Tensor(c!)? obj_history, "
@@ -2557,8 +2472,6 @@ TORCH_LIBRARY_IMPL(ainp, CUDA, m) {
   m.impl("ar_extrapolate", &ar_extrapolate);
   m.impl("janssen_windows", &janssen_windows);
   m.impl("janssen_ola", &janssen_ola);
-  m.impl("janssen_windows_mask", &janssen_windows_mask);
-  m.impl("janssen_ola_mask", &janssen_ola_mask);
   m.impl("spain", &spain);
   m.impl("spain_omp", &spain_omp);
   m.impl("spain_learned", &spain_learned);
@@ -2661,8 +2574,6 @@ TORCH_LIBRARY_IMPL(ainp, Autograd, m) {
   m.impl("ar_extrapolate", torch::CppFunction::makeFallthrough());
   m.impl("janssen_windows", torch::CppFunction::makeFallthrough());
   m.impl("janssen_ola", torch::CppFunction::makeFallthrough());
-  m.impl("janssen_windows_mask", torch::CppFunction::makeFallthrough());
-  m.impl("janssen_ola_mask", torch::CppFunction::makeFallthrough());
   m.impl("spain", torch::CppFunction::makeFallthrough());
   m.impl("spain_omp", torch::CppFunction::makeFallthrough());
   m.impl("spain_learned", torch::CppFunction::makeFallthrough());

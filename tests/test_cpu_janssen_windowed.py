@@ -240,14 +240,14 @@ def _check(f, name, order, good, einval, empty):
 
 def test_janssen_windows_bad_arguments_fail_without_launching():
     from ainp import _lib
-    order = ["signals", "total", "sig_off", "row_tab", "gap_start", "gap_len", "n_rows", "w", "a",
-             "gana", "n_shapes", "sol", "stride", "stream"]
-    good = dict(signals=ONE, total=1000, sig_off=ONE, row_tab=ONE, gap_start=ONE, gap_len=ONE,
-                n_rows=4, w=256, a=64, gana=ONE, n_shapes=1, sol=ONE, stride=256, stream=None)
-    einval = [dict(signals=None), dict(sig_off=None), dict(row_tab=None), dict(gap_start=None),
-              dict(gap_len=None), dict(gana=None), dict(sol=None), dict(total=0),
-              dict(n_rows=-1), dict(a=60), dict(a=0), dict(a=256), dict(w=1, a=1),
-              dict(w=32768, a=1024, stride=32768), dict(n_shapes=0), dict(stride=255)]
+    order = ["signals", "missing", "total", "sig_off", "row_tab", "n_rows", "w", "a", "gana",
+             "n_shapes", "sol", "stride", "stream"]
+    good = dict(signals=ONE, missing=ONE, total=1000, sig_off=ONE, row_tab=ONE, n_rows=4, w=256,
+                a=64, gana=ONE, n_shapes=1, sol=ONE, stride=256, stream=None)
+    einval = [dict(signals=None), dict(missing=None), dict(sig_off=None), dict(row_tab=None),
+              dict(gana=None), dict(sol=None), dict(total=0), dict(n_rows=-1), dict(a=60),
+              dict(a=0), dict(a=256), dict(w=1, a=1), dict(w=32768, a=1024, stride=32768),
+              dict(n_shapes=0), dict(stride=255), dict(n_rows=1 << 31)]
     _check(_lib.lib.ainp_janssen_windows, b"ainp_janssen_windows", order, good, einval,
            dict(n_rows=0))
 
@@ -255,22 +255,28 @@ def test_janssen_windows_bad_arguments_fail_without_launching():
 def test_janssen_ola_bad_arguments_fail_without_launching():
     from ainp import _lib
     order = ["sol", "n_rows", "stride", "row_history", "maxit", "hist_stride", "row_tab",
-             "gap_start", "gap_len", "gap_off", "gap_tab", "n_gaps", "h_max", "w", "a", "gana",
-             "gsyn", "n_shapes", "signals", "total", "history", "out_stride", "stream"]
+             "gap_start", "gap_len", "miss_off", "miss_idx", "n_idx", "win_row", "n_tab",
+             "unit_off", "unit_tab", "n_units", "h_max", "w", "a", "gana", "gsyn", "n_shapes",
+             "signals", "total", "history", "out_stride", "stream"]
     good = dict(sol=ONE, n_rows=6, stride=256, row_history=ONE, maxit=5, hist_stride=80,
-                row_tab=ONE, gap_start=ONE, gap_len=ONE, gap_off=ONE, gap_tab=ONE, n_gaps=1,
-                h_max=80, w=256, a=64, gana=ONE, gsyn=ONE, n_shapes=1, signals=ONE, total=2000,
-                history=ONE, out_stride=80, stream=None)
+                row_tab=ONE, gap_start=ONE, gap_len=ONE, miss_off=ONE, miss_idx=ONE, n_idx=40,
+                win_row=ONE, n_tab=35, unit_off=ONE, unit_tab=ONE, n_units=2, h_max=80, w=256,
+                a=64, gana=ONE, gsyn=ONE, n_shapes=1, signals=ONE, total=2000, history=ONE,
+                out_stride=80, stream=None)
     einval = [dict(sol=None), dict(row_tab=None), dict(gap_start=None), dict(gap_len=None),
-              dict(gap_off=None), dict(gap_tab=None), dict(gana=None), dict(gsyn=None),
-              dict(signals=None), dict(total=0), dict(n_rows=-1), dict(n_gaps=-1), dict(a=60),
-              dict(a=256), dict(w=32768, a=1024, stride=32768), dict(n_shapes=0),
-              dict(stride=255), dict(h_max=0), dict(h_max=2049, out_stride=2049),
-              dict(history=None), dict(row_history=None), dict(maxit=0), dict(maxit=1001),
-              dict(hist_stride=0), dict(out_stride=79)]
-    _check(_lib.lib.ainp_janssen_ola, b"ainp_janssen_ola", order, good, einval, dict(n_gaps=0))
+              dict(miss_off=None), dict(miss_idx=None), dict(win_row=None), dict(unit_off=None),
+              dict(unit_tab=None), dict(gana=None), dict(gsyn=None), dict(signals=None),
+              dict(total=0), dict(n_rows=-1), dict(n_units=-1), dict(n_idx=-1), dict(n_tab=-1),
+              dict(a=60), dict(a=256), dict(w=32768, a=1024, stride=32768), dict(n_shapes=0),
+              dict(stride=255), dict(h_max=0), dict(h_max=2001, out_stride=2001),
+              dict(h_max=2049, out_stride=2049), dict(history=None), dict(row_history=None),
+              dict(maxit=0), dict(maxit=1001), dict(hist_stride=0), dict(out_stride=79),
+              dict(n_units=1 << 31), dict(n_rows=1 << 31),
+              dict(h_max=1 << 24, total=1 << 25, out_stride=1 << 24)]
+    _check(_lib.lib.ainp_janssen_ola, b"ainp_janssen_ola", order, good, einval,
+           dict(n_units=0))
     # without a history neither maxit nor the strides matter
-    assert _lib.lib.ainp_janssen_ola(*(dict(good, n_gaps=0, history=None, row_history=None,
+    assert _lib.lib.ainp_janssen_ola(*(dict(good, n_units=0, history=None, row_history=None,
                                             maxit=0, hist_stride=0, out_stride=0)[k]
                                        for k in order)) == 0
 

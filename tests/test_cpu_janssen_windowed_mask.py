@@ -1,7 +1,8 @@
 """Host-side tests of window-wise Janssen on whole signals with any mask
-(ainp.janssen.plan_windows_mask / janssen_windowed_mask, the argument checks of
-ainp_janssen_windows_mask and ainp_janssen_ola_mask) and of their test-only
-reference tests/janssen_windowed_mask_ref.py.  No GPU.
+(ainp.janssen.plan_windows_mask / janssen_windowed_mask; the argument checks of
+the gather and the overlap-add, which it shares with the per-gap layout, are in
+tests/test_cpu_janssen_windowed.py) and of their test-only reference
+tests/janssen_windowed_mask_ref.py.  No GPU.
 
 test_reference_bounds_the_parity_cases re-measures, on the cases of the GPU
 parity test, what the bound 1e-9 * max|clean missing| rests on: every row
@@ -9,7 +10,6 @@ completes all its iterations, Cholesky against LU moves the result by at most
 1e-10 of the largest missing sample, rounding the input to float32 by at least
 1e-8.  DESIGN §14 records the figures.
 """
-import ctypes
 import inspect
 
 import numpy as np
@@ -18,9 +18,6 @@ import pytest
 import janssen_ref as R
 import janssen_windowed_mask_ref as WM
 import janssen_windowed_ref as W
-
-ONE = ctypes.c_void_p(16)            # a non-null stand-in, never dereferenced
-
 
 def _plan(name, wtypes=("hann",)):
     from ainp.janssen import plan_windows_mask
@@ -53,7 +50,7 @@ def _plan_rows(plan):
         else:
             where = plan.miss_idx[plan.miss_off[r]:plan.miss_off[r + 1]]
             assert plan.gap_len[r] == 0
-        rows[int(plan.row_tab[r, 2])] = where
+        rows[int(plan.row_tab[r, 4])] = where
     return rows
 
 
@@ -67,13 +64,14 @@ def test_planner_rows_are_the_reference_windows(name):
         assert np.array_equal(got[s], want[s]), (name, s)
     w, a, _, _, n, runs, _ = WM.CASES[name]
     L = -(-n // a) * a + (w // a - 1) * a
-    assert np.all(plan.row_tab[:, 0] == n) and np.all(plan.row_tab[:, 1] == L)
+    assert np.all(plan.row_tab[:, 0] == n) and np.all(plan.row_tab[:, 3] == L)
+    assert np.all(plan.row_tab[:, 1] == 0) and np.all(plan.row_tab[:, 2] == n)
     # one-run rows first, each part in window order; the table finds every row
-    assert np.all(np.diff(plan.row_tab[:plan.n_one, 2]) > 0)
-    assert np.all(np.diff(plan.row_tab[plan.n_one:, 2]) > 0)
+    assert np.all(np.diff(plan.row_tab[:plan.n_one, 4]) > 0)
+    assert np.all(np.diff(plan.row_tab[plan.n_one:, 4]) > 0)
     assert len(plan.win_row) == L // a
     for r in range(len(plan)):
-        assert plan.win_row[plan.row_tab[r, 2]] == r
+        assert plan.win_row[plan.row_tab[r, 4]] == r
     assert np.count_nonzero(plan.win_row >= 0) == len(plan)
     assert plan.run_tab.tolist() == [[e - s, s, L, 0, 0] for s, e in runs]
     assert plan.run_off.tolist() == [s for s, _ in runs]
@@ -104,7 +102,7 @@ def test_the_wrap_row_lists_the_tail_before_the_head():
     r = plan.n_one
     # n = 508, L = 540, window 35 starts at 503: the tail [505, 508) at 2 .. 4,
     # then, through the wrap, the head [0, 4) at 37 .. 40
-    assert plan.row_tab[r].tolist() == [508, 540, 35, 0]
+    assert plan.row_tab[r].tolist() == [508, 0, 508, 540, 35, 0]
     assert plan.lists()[0].tolist() == [2, 3, 4, 37, 38, 39, 40]
     assert plan.win_row[35] == r
 
@@ -124,7 +122,7 @@ def test_planner_batches_shapes_and_signals():
     assert plan.run_signal.tolist() == [0, 0, 1] * 3
     assert plan.run_off.tolist() == [k * 4000 + o for k in range(3) for o in (900, 960, 2900)]
     for r in range(len(plan)):
-        _, _, win, k = plan.row_tab[r]
+        _, _, _, _, win, k = plan.row_tab[r]
         i = (plan.sig_off[r] - k * 4000) // 2000
         assert plan.win_row[(k * 2 + i) * S + win] == r
 
@@ -167,7 +165,7 @@ def test_refusals():
 
 def test_signatures_and_registration():
     import torch
-    from ainp import ops
+    from ainp import _lib, ops
     from ainp.janssen import janssen_windowed, janssen_windowed_mask, plan_windows_mask
     from models import model_eval
     import models.AudioReg as AR
@@ -183,65 +181,13 @@ def test_signatures_and_registration():
     assert [(k, v.default) for k, v in ev.items()][2:] == [
         ("gaps", ((2.0, 0.08),)), ("p", 512), ("w", 4096), ("a", 1024), ("wtype", "hann"),
         ("maxit", 20), ("method", "lpc")]
-    assert callable(ops.janssen_windows_mask) and callable(ops.janssen_ola_mask)
-    assert hasattr(torch.ops.ainp, "janssen_windows_mask")
-    assert hasattr(torch.ops.ainp, "janssen_ola_mask")
-
-
-# ---------------------------------------------------------------- the C ABI
-def _check(f, name, order, good, einval, empty):
-    from ainp import _lib
-
-    def call(**kw):
-        a = dict(good, **kw)
-        return f(*(a[k] for k in order))
-
-    for kw in einval:
-        assert call(**kw) == -1, kw                               # AINP_EINVAL
-        assert name in _lib.lib.ainp_last_error(), kw
-    assert call(**empty) == 0            # an empty batch is a no-op, still no launch
-
-
-def test_janssen_windows_mask_bad_arguments_fail_without_launching():
-    from ainp import _lib
-    order = ["signals", "missing", "total", "sig_off", "row_tab", "n_rows", "w", "a", "gana",
-             "n_shapes", "sol", "stride", "stream"]
-    good = dict(signals=ONE, missing=ONE, total=1000, sig_off=ONE, row_tab=ONE, n_rows=4, w=256,
-                a=64, gana=ONE, n_shapes=1, sol=ONE, stride=256, stream=None)
-    einval = [dict(signals=None), dict(missing=None), dict(sig_off=None), dict(row_tab=None),
-              dict(gana=None), dict(sol=None), dict(total=0), dict(n_rows=-1), dict(a=60),
-              dict(a=0), dict(a=256), dict(w=1, a=1), dict(w=32768, a=1024, stride=32768),
-              dict(n_shapes=0), dict(stride=255), dict(n_rows=1 << 31)]
-    _check(_lib.lib.ainp_janssen_windows_mask, b"ainp_janssen_windows_mask", order, good, einval,
-           dict(n_rows=0))
-
-
-def test_janssen_ola_mask_bad_arguments_fail_without_launching():
-    from ainp import _lib
-    order = ["sol", "n_rows", "stride", "row_history", "maxit", "hist_stride", "row_tab",
-             "gap_start", "gap_len", "miss_off", "miss_idx", "n_idx", "win_row", "n_tab",
-             "run_off", "run_tab", "n_runs", "h_max", "w", "a", "gana", "gsyn", "n_shapes",
-             "signals", "total", "history", "out_stride", "stream"]
-    good = dict(sol=ONE, n_rows=6, stride=256, row_history=ONE, maxit=5, hist_stride=80,
-                row_tab=ONE, gap_start=ONE, gap_len=ONE, miss_off=ONE, miss_idx=ONE, n_idx=40,
-                win_row=ONE, n_tab=35, run_off=ONE, run_tab=ONE, n_runs=2, h_max=80, w=256, a=64,
-                gana=ONE, gsyn=ONE, n_shapes=1, signals=ONE, total=2000, history=ONE,
-                out_stride=80, stream=None)
-    einval = [dict(sol=None), dict(row_tab=None), dict(gap_start=None), dict(gap_len=None),
-              dict(miss_off=None), dict(miss_idx=None), dict(win_row=None), dict(run_off=None),
-              dict(run_tab=None), dict(gana=None), dict(gsyn=None), dict(signals=None),
-              dict(total=0), dict(n_rows=-1), dict(n_runs=-1), dict(n_idx=-1), dict(n_tab=-1),
-              dict(a=60), dict(a=256), dict(w=32768, a=1024, stride=32768), dict(n_shapes=0),
-              dict(stride=255), dict(h_max=0), dict(h_max=2001, out_stride=2001),
-              dict(history=None), dict(row_history=None), dict(maxit=0), dict(maxit=1001),
-              dict(hist_stride=0), dict(out_stride=79), dict(n_runs=1 << 31),
-              dict(h_max=1 << 24, total=1 << 25, out_stride=1 << 24)]
-    _check(_lib.lib.ainp_janssen_ola_mask, b"ainp_janssen_ola_mask", order, good, einval,
-           dict(n_runs=0))
-    # without a history neither maxit nor the strides matter
-    assert _lib.lib.ainp_janssen_ola_mask(*(dict(good, n_runs=0, history=None, row_history=None,
-                                                 maxit=0, hist_stride=0, out_stride=0)[k]
-                                            for k in order)) == 0
+    # one gather and one overlap-add for every plan: the any-mask pair is gone
+    for name in ("janssen_windows_mask", "janssen_ola_mask"):
+        assert not hasattr(ops, name) and not hasattr(torch.ops.ainp, name)
+        assert not hasattr(_lib.lib, "ainp_" + name)
+    for name in ("janssen_windows", "janssen_ola"):
+        assert callable(getattr(ops, name)) and hasattr(torch.ops.ainp, name)
+        assert hasattr(_lib.lib, "ainp_" + name)
 
 
 # ------------------------------------------------------------ the reference

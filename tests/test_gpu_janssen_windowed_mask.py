@@ -1,6 +1,6 @@
 """GPU tests of window-wise Janssen on whole signals with any mask
-(ainp_janssen_windows_mask and ainp_janssen_ola_mask of csrc/janssen_windows.hip
-around ainp_janssen_ex and ainp_janssen_mask, through
+(ainp_janssen_windows and ainp_janssen_ola of csrc/janssen_windows.hip around
+ainp_janssen_ex and ainp_janssen_mask, through
 ainp.janssen.janssen_windowed_mask and
 models/model_eval.run_janssen_windowed_mask_evaluation) against the dense
 float64 transcription of segmentation_inp.m in tests/janssen_windowed_mask_ref.py.
@@ -172,7 +172,7 @@ def test_batch_of_signals_and_shapes_is_the_separate_calls():
 def _count_launches(monkeypatch):
     from ainp import ops
     calls = {}
-    for name in ("janssen", "janssen_mask", "janssen_windows_mask", "janssen_ola_mask"):
+    for name in ("janssen", "janssen_mask", "janssen_windows", "janssen_ola"):
         calls[name] = 0
 
         def counted(*args, _f=getattr(ops, name), _name=name, **kw):
@@ -190,8 +190,7 @@ def test_one_launch_each(monkeypatch):
     plan = plan_windows_mask(masks, wtypes=WM.WTYPES, **{k: BATCH_KW[k] for k in "pwa"})
     assert 0 < plan.n_one < len(plan)                         # a mixed batch
     janssen_windowed_mask(sigs, masks, wtype=WM.WTYPES, return_history=True, **BATCH_KW)
-    assert calls == {"janssen": 1, "janssen_mask": 1, "janssen_windows_mask": 1,
-                     "janssen_ola_mask": 1}
+    assert calls == {"janssen": 1, "janssen_mask": 1, "janssen_windows": 1, "janssen_ola": 1}
     # no list rows: the banded solver is not launched
     names = ("single_gap", "both_ends")
     sigs = [WM.case_signal(n) for n in names]
@@ -199,8 +198,7 @@ def test_one_launch_each(monkeypatch):
     plan = plan_windows_mask(masks, p=32, w=256, a=64, wtypes=WM.WTYPES)
     assert plan.n_one == len(plan) > 0
     janssen_windowed_mask(sigs, masks, p=32, w=256, a=64, maxit=2, wtype=WM.WTYPES)
-    assert calls == {"janssen": 2, "janssen_mask": 1, "janssen_windows_mask": 2,
-                     "janssen_ola_mask": 2}
+    assert calls == {"janssen": 2, "janssen_mask": 1, "janssen_windows": 2, "janssen_ola": 2}
 
 
 def test_silent_signal_gives_zero_runs():
@@ -219,47 +217,59 @@ def test_silent_signal_gives_zero_runs():
 
 def test_ops_refuse_bad_tables():
     from ainp import ops
-    from ainp.janssen import plan_windows_mask
+    from ainp.janssen import plan_windows, plan_windows_mask
     name = "two_runs_one_window"
     w, a, p = 256, 64, 32
     plan = plan_windows_mask([WM.case_mask(name)], p=p, w=w, a=a)
+    tabs = plan.tables()
     sig = torch.from_numpy(WM.case_signal(name)).cuda()
-    miss = torch.from_numpy(plan.missing).cuda()
-    sol = ops.janssen_windows_mask(sig, miss, plan.sig_off, plan.row_tab, w, a, plan.gana)
+    miss = torch.from_numpy(tabs.missing).cuda()
+    sol = ops.janssen_windows(sig, miss, tabs, w, a, plan.gana)
     assert sol.shape == (5, w)
-    bad = plan.row_tab.copy()
-    bad[0, 2] = 35                                            # window 35 of 35
-    with pytest.raises(ValueError):
-        ops.janssen_windows_mask(sig, miss, plan.sig_off, bad, w, a, plan.gana)
-    with pytest.raises(ValueError):
-        ops.janssen_windows_mask(sig, miss, plan.sig_off + 1, plan.row_tab, w, a, plan.gana)
-    with pytest.raises(ValueError):
-        ops.janssen_windows_mask(sig, miss[:-1], plan.sig_off, plan.row_tab, w, a, plan.gana)
-    with pytest.raises(TypeError):
-        ops.janssen_windows_mask(sig, miss.double(), plan.sig_off, plan.row_tab, w, a, plan.gana)
 
-    def ola(**kw):
-        t = dict(row_tab=plan.row_tab, gap_start=plan.gap_start, gap_len=plan.gap_len,
-                 miss_off=plan.miss_off, miss_idx=plan.miss_idx, win_row=plan.win_row,
-                 run_off=plan.run_off, run_tab=plan.run_tab)
-        t.update(kw)
-        return ops.janssen_ola_mask(sol, None, t["row_tab"], t["gap_start"], t["gap_len"],
-                                    t["miss_off"], t["miss_idx"], t["win_row"], t["run_off"],
-                                    t["run_tab"], a, plan.gana, plan.gsyn, sig.clone())
-    assert ola() is None
-    win_row = plan.win_row.copy()
-    win_row[0] = 5
-    run_tab = plan.run_tab.copy()
-    run_tab[0, 3] = 1                                         # its table would end past win_row
-    idx = plan.miss_idx.copy()
-    idx[1] = idx[0]
-    gap_len = plan.gap_len.copy()
-    gap_len[0] = 0                                            # neither a run nor a list
-    for kw in (dict(win_row=win_row), dict(run_tab=run_tab), dict(miss_idx=idx),
-               dict(gap_len=gap_len), dict(run_off=plan.run_off + 2000),
-               dict(miss_off=plan.miss_off[:-1])):
+    def row(r, col, value):
+        bad = tabs.row_tab.copy()
+        bad[r, col] = value
+        return tabs._replace(row_tab=bad)
+    # window 35 of 35; a support longer than its circle; a signal that ends past the buffer
+    for bad in (row(0, 4, 35), row(0, 2, 2241), row(0, 0, 2001),
+                tabs._replace(sig_off=tabs.sig_off + 1)):
         with pytest.raises(ValueError):
-            ola(**kw)
+            ops.janssen_windows(sig, miss, bad, w, a, plan.gana)
+    with pytest.raises(ValueError):
+        ops.janssen_windows(sig, miss[:-1], tabs, w, a, plan.gana)
+    with pytest.raises(TypeError):
+        ops.janssen_windows(sig, miss.double(), tabs, w, a, plan.gana)
+
+    def ola(t):
+        return ops.janssen_ola(sol, None, t, a, plan.gana, plan.gsyn, sig.clone())
+    assert ola(tabs) is None
+    win_row = tabs.win_row.copy()
+    win_row[0] = 5
+    unit_tab = tabs.unit_tab.copy()
+    unit_tab[0, 3] = 1                                        # its table would end past win_row
+    idx = tabs.miss_idx.copy()
+    idx[1] = idx[0]
+    gap_len = tabs.gap_len.copy()
+    gap_len[0] = 0                                            # neither a run nor a list
+    for kw in (dict(win_row=win_row), dict(unit_tab=unit_tab), dict(miss_idx=idx),
+               dict(gap_len=gap_len), dict(unit_off=tabs.unit_off + 2000),
+               dict(miss_off=tabs.miss_off[:-1])):
+        with pytest.raises(ValueError):
+            ola(tabs._replace(**kw))
+    for bad in (row(0, 2, 2241), row(0, 0, 2001)):            # the overlap-add checks the rows too
+        with pytest.raises(ValueError):
+            ola(bad)
+    # the per-gap layout goes through the same checks: a support longer than its circle, a
+    # signal outside the buffer
+    plan = plan_windows([WM.case_mask("single_gap")], p=p, w=w, a=a)
+    tabs = plan.tables()
+    miss = torch.from_numpy(tabs.missing).cuda()
+    assert ops.janssen_windows(sig, miss, tabs, w, a, plan.gana).shape == (6, w)
+    L = int(tabs.row_tab[0, 3])
+    for bad in (row(0, 2, L + 1), row(0, 0, 2001), tabs._replace(sig_off=tabs.sig_off - 1)):
+        with pytest.raises(ValueError):
+            ops.janssen_windows(sig, miss, bad, w, a, plan.gana)
 
 
 def _clip_with_two_gaps(clip):

@@ -197,8 +197,9 @@ def test_h_is_what_it_was():
         assert np.array_equal(info[0]["objective"], old_info[0]["objective"], equal_nan=True)
         # and the launch below it: the rows of the plan through ops.spain
         dbuf = torch.from_numpy(x.copy()).cuda()
-        sol = ops.janssen_windows(dbuf, plan.sig_off, plan.row_tab, plan.gap_start, plan.gap_len,
-                                  plan.w, plan.a, plan.gana)
+        tabs = plan.tables()
+        sol = ops.janssen_windows(dbuf, torch.from_numpy(tabs.missing).cuda(), tabs, plan.w,
+                                  plan.a, plan.gana)
         iters, hist = ops.spain(sol, plan.gap_start, plan.gap_len, algorithm=alg,
                                 return_history=True)
         assert iters.cpu().tolist() == info[0]["iters"]

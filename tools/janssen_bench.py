@@ -42,12 +42,15 @@ of the gather and the overlap-add are on the device before the timed window;
 the Janssen launch goes through ops.janssen as the gap-wise one does.  It
 prints how many windows (rows) the batch makes and how many rounds of 256
 workgroups (one per CU) that is.  --history also writes every iteration.  No
-CPU run.
+CPU run.  --any-mask plans the same batch with plan_windows_mask (the fixed grid
+of the whole signal, 5 rows a gap, no per-gap support): the same three launches
+over the other plan's tables.
 
 Usage: python tools/janssen_bench.py [--reps 5] [--threads 16] [--no-cpu] [--fit]
            [--method lpc|arburg]
            [--algorithm janssen|extrapolation|janssen_hann|janssen_rect|janssen_tukey]
-           [--a 1024] [--history] [--orders 256,512] [--batches 1,256] [--burg-steps]
+           [--a 1024] [--history] [--any-mask] [--orders 256,512] [--batches 1,256]
+           [--burg-steps]
 """
 import argparse
 import json
@@ -141,7 +144,7 @@ def time_gpu(batch, n, s, h, p, maxit, reps, method="lpc", algorithm="janssen"):
     return statistics.median(ts), min(ts), max(ts), sol[0].cpu().numpy()
 
 
-def time_windowed(batch, n, s, h, p, maxit, reps, method, wtype, a, history):
+def time_windowed(batch, n, s, h, p, maxit, reps, method, wtype, a, history, any_mask=False):
     """One gap [s, s + h) in each of `batch` signals -> {launch: (median, min,
     max) ms} for the three launches, the number of rows, iterations done."""
     import torch
@@ -152,11 +155,14 @@ def time_windowed(batch, n, s, h, p, maxit, reps, method, wtype, a, history):
     mask[s:s + h] = False
     for x in sigs:
         x[s:s + h] = 0.0
-    plan = jn.plan_windows([mask] * batch, p, W, a, (wtype,))
+    plan = (jn.plan_windows_mask if any_mask else jn.plan_windows)([mask] * batch, p, W, a,
+                                                                   (wtype,))
+    assert np.all(plan.gap_len >= 1)                # one run a row: all through ops.janssen
     up = lambda t: torch.from_numpy(np.ascontiguousarray(t)).cuda()
     buf0 = up(np.concatenate(sigs))
-    so, rt, gs, gl = up(plan.sig_off), up(plan.row_tab), up(plan.gap_start), up(plan.gap_len)
-    go, gt, gana, gsyn = up(plan.gap_off), up(plan.gap_tab), up(plan.gana), up(plan.gsyn)
+    tabs = plan.tables()._replace(miss_idx=np.zeros(1, np.int32))
+    miss, so, rt, *ola_tabs = (up(t) for t in tabs)
+    gana, gsyn = up(plan.gana), up(plan.gsyn)
     rows = len(plan)
     ts = {"gather": [], "janssen": [], "ola": []}
     for r in range(reps + 1):
@@ -167,12 +173,12 @@ def time_windowed(batch, n, s, h, p, maxit, reps, method, wtype, a, history):
         torch.cuda.synchronize()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
-        T.janssen_windows(buf, so, rt, gs, gl, a, gana, sol)
+        T.janssen_windows(buf, miss, so, rt, a, gana, sol)
         ev[1].record()
         iters, rhist = ops.janssen(sol, [W] * rows, plan.gap_start, plan.gap_len, p, maxit,
                                    return_history=history, method=method)
         ev[2].record()
-        T.janssen_ola(sol, rhist, rt, gs, gl, go, gt, h, a, gana, gsyn, buf, out)
+        T.janssen_ola(sol, rhist, rt, *ola_tabs, h, a, gana, gsyn, buf, out)
         ev[3].record()
         torch.cuda.synchronize()
         if r:
@@ -187,15 +193,17 @@ def windowed_table(args, n):
     import torch
     wtype = args.algorithm[len("janssen_"):]
     print(f"{torch.cuda.get_device_name(0)}; {args.algorithm} {args.method}, w = {W}, "
-          f"a = {args.a}, n = {n}, h = {H}, maxit = {MAXIT}, history = {args.history}",
+          f"a = {args.a}, n = {n}, h = {H}, maxit = {MAXIT}, history = {args.history}, "
+          f"any mask = {args.any_mask}",
           flush=True)
     for p in args.orders:
         for batch in args.batches:
             t, rows, iters = time_windowed(batch, n, W, H, p, MAXIT, args.reps, args.method,
-                                           wtype, args.a, args.history)
+                                           wtype, args.a, args.history, args.any_mask)
             gap, glo, ghi, _ = time_gpu(batch, n, W, H, p, MAXIT, args.reps, args.method)
             rounds = -(-rows // 256)
-            row = dict(algorithm=args.algorithm, method=args.method, p=p, a=args.a, gaps=batch,
+            row = dict(algorithm=args.algorithm, any_mask=args.any_mask, method=args.method, p=p,
+                       a=args.a, gaps=batch,
                        rows=rows, workgroup_rounds=rounds, iters_min=iters[0],
                        iters_max=iters[1], history=args.history,
                        gap_wise_launch_ms=round(gap, 3), gap_wise_launch_ms_min=round(glo, 3),
@@ -262,6 +270,7 @@ def main():
                              "janssen_tukey"))
     ap.add_argument("--a", type=int, default=1024)
     ap.add_argument("--history", action="store_true")
+    ap.add_argument("--any-mask", action="store_true")
     ap.add_argument("--orders", type=lambda v: tuple(int(t) for t in v.split(",")), default=ORDERS)
     ap.add_argument("--batches", type=lambda v: tuple(int(t) for t in v.split(",")),
                     default=BATCHES)
